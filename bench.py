@@ -14,7 +14,13 @@ double-buffered stream ("gather_to_rank0") and the frame-parallel rate (each ran
 frame, "weak_scaling"). DepthOfField 4K (--config dof4k) is the render-bound scaling
 config; the TwoSpheresPlane 1080p frame is the metric's.
 
-Launch: python bench.py [--steps K --warmup W]          (N = 1)
+A plain run does what the value needs and no more: setup, clock and step warm-up, the K
+timed steps, the result line. --full adds every other measurement to the line: the CPU
+baselines, the kernel's own duration from HIP events (frame_ms), the uint8 frame (rgb8), the
+ray census and the roofline, and at N > 1 the frame streams, the per-rank render times, weak
+scaling and the scaling config. --dump-outputs DIR writes the last timed frame as .npy.
+
+Launch: python bench.py [--steps K --warmup W] [--full] [--dump-outputs DIR]     (N = 1)
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 import argparse
@@ -76,9 +82,15 @@ def parse():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--config", default="tsp1080", choices=sorted(CONFIGS))
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the value does not need: CPU baselines, kernel duration (frame_ms), "
+                        "uint8 frame, ray census + roofline; at N > 1 the frame streams, weak scaling, scaling config")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the frame the last timed step computed to DIR/<name>.npy (float32, at most 64 MB; "
+                        "a larger frame as a fixed seeded sample of its rows, listed in DIR/<name>_rows.npy)")
     p.add_argument("--cpu-seconds", type=float, default=10.0,
-                   help="budget of the C-restatement CPU line (0 = skip both CPU lines)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+                   help="--full: budget of the C-restatement CPU line (0 = skip both CPU lines)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU lines")
     p.add_argument("--clock-warmup-s", type=float, default=0.3,
                    help="untimed sustained rendering before the warm-up steps, so the GPU clocks settle")
     p.add_argument("--force-dist", action="store_true", help="initialise torch.distributed even for one rank (tests)")
@@ -89,6 +101,32 @@ def parse():
     p.add_argument("--pmc-json", default=None,
                    help="tools/pmc_summary.py output for this config (default profiles/pmc_<config>.json)")
     return p.parse_args()
+
+
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each of `arrays` (name -> tensor, first axis = image rows) as
+    dirname/<name>.npy, float64 kept and every other dtype as float32. An array over its share
+    of DUMP_BYTES is cut to a fixed sample of its rows (RandomState(0), ascending), whose
+    indices go to dirname/<name>_rows.npy, so two runs with the same arguments write the same
+    pixels. Returns {file name: shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    written = {}
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy()
+        x = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
+        fit = (share - 1024) // (x[0].nbytes + 8)  # (1 KiB for the two .npy headers, 8 B per row index)
+        if x.shape[0] > fit:
+            rows = np.sort(np.random.RandomState(0).choice(x.shape[0], fit, replace=False))
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+            written[name + "_rows.npy"] = [len(rows)]
+            x = x[rows]
+        np.save(os.path.join(dirname, name + ".npy"), x)
+        written[name + ".npy"] = list(x.shape)
+    return written
 
 
 def pmc_traffic(path):
@@ -316,7 +354,7 @@ def root_shares(world):
 
 
 def sharded_frame(sc, rank, world, steps, warmup, use_dist, device, sync=cuda_sync, stream=None, render_rows=None,
-                  graph=True, collective_at_one=False, tune=True):
+                  graph=True, collective_at_one=False, tune=True, host_issue=True):
     """ONE frame sharded over the ranks per step (the N > 1 value; rtx.distributed.FrameGraph):
     every step renders this rank's rows of the frame straight to uint8 (fused, one launch),
     gathers them to rank 0 (one RCCL collective) and, for interleaved rows, puts them in
@@ -363,17 +401,19 @@ def sharded_frame(sc, rank, world, steps, warmup, use_dist, device, sync=cuda_sy
     # the timed region: `steps` frames, issued from C (rtx_graph_launch, fg.kmax frames per
     # graph launch; each frame rendered, gathered and reordered before the next starts)
     s = timed(lambda: fg.run(steps, stream), 1, use_dist, sync, device)
-    # host issue per frame (outside the timed region): the clock stopped before the device
-    # finishes, for run() and for one Python step() per frame
-    t0 = time.perf_counter()
-    fg.run(steps, stream)
-    t1 = time.perf_counter()
-    sync()
-    t2 = time.perf_counter()
-    for _ in range(steps):
-        fg.step()
-    t3 = time.perf_counter()
-    sync()
+    # host issue per frame (outside the timed region, host_issue: two more runs of `steps`
+    # frames): the clock stopped before the device finishes, for run() and for one Python
+    # step() per frame
+    if host_issue:
+        t0 = time.perf_counter()
+        fg.run(steps, stream)
+        t1 = time.perf_counter()
+        sync()
+        t2 = time.perf_counter()
+        for _ in range(steps):
+            fg.step()
+        t3 = time.perf_counter()
+        sync()
     last = fg.frame()
     nrows = [len(r) for r in fg.g.rows]
     if fg.interleave:
@@ -386,9 +426,10 @@ def sharded_frame(sc, rank, world, steps, warmup, use_dist, device, sync=cuda_sy
         part = "contiguous row blocks (np.array_split), one gather to rank 0"
     info = {"graph": fg.graph is not None, "frames_per_graph": fg.kmax if fg.graphk is not None else 1,
             "rows_per_rank": nrows if len(nrows) <= 16 else [min(nrows), max(nrows)],
-            "partition": part, "in_order": bool(fg.g.in_order),
-            "host_issue_us_per_frame": round((t1 - t0) * 1e6 / steps, 3),
-            "host_issue_step_us_per_frame": round((t3 - t2) * 1e6 / steps, 3)}
+            "partition": part, "in_order": bool(fg.g.in_order)}
+    if host_issue:
+        info.update(host_issue_us_per_frame=round((t1 - t0) * 1e6 / steps, 3),
+                    host_issue_step_us_per_frame=round((t3 - t2) * 1e6 / steps, 3))
     if tuning:
         info["root_share_tuning"] = tuning
     return s, (last.clone() if last is not None else None), info
@@ -532,7 +573,7 @@ def main():
         if world == 1 and a.gpus > 1:
             sys.exit("--gpus %d needs torch.distributed.run with %d processes" % (a.gpus, a.gpus))
     cpu = {}
-    if world == 1 and not a.no_cpu_baseline and a.cpu_seconds > 0:
+    if a.full and world == 1 and not a.no_cpu_baseline and a.cpu_seconds > 0:
         # host baselines first, before this process touches the GPU (the Python loop forks)
         cpu["cpu_baseline"] = cpu_baseline(a.config)
         cpu["cpu_baseline_native"] = cpu_baseline_native(a.config, a.cpu_seconds)
@@ -594,40 +635,46 @@ def main():
              "note": "outside the timed region; first_frame_ms includes one render; specialized_ready_ms: from the "
                      "first frame's start to the end of the first frame with the specialized kernel"}
 
-    # ray-segment census for the algorithmic byte model (separate counting launch)
-    cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
-    sc.render_device(out=fb, counters=cnt)
-    c = cnt.cpu().numpy()
-    sc.jit_wait()  # (no compile left running on a host thread during the timed regions)
-    cast_rays = int(c[:10].sum())
-    shadow_rays = int(c[10])
-    segments = cast_rays + shadow_rays
-    b_alg = 32 * segments + 12 * W * H  # 32 B per segment + 12 B/pixel fp32 RGB
+    if a.full:
+        # ray-segment census for the algorithmic byte model (separate counting launch)
+        cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
+        sc.render_device(out=fb, counters=cnt)
+        c = cnt.cpu().numpy()
+        sc.jit_wait()  # (no compile left running on a host thread during the timed regions)
+        cast_rays = int(c[:10].sum())
+        shadow_rays = int(c[10])
+        segments = cast_rays + shadow_rays
+        b_alg = 32 * segments + 12 * W * H  # 32 B per segment + 12 B/pixel fp32 RGB
 
     def full_frame():
         sc.render_device(out=fb, stream=stream)
 
     extra = {}
+    dump = {}  # --dump-outputs: what the last timed step left its caller (host copies)
     if world == 1 and not a.pipeline:
         # N = 1: one step = one whole frame into the fp32 framebuffer
-        fb8 = torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
+        if a.full:
+            fb8 = torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
 
-        def frame_u8():
-            sc.render_device(out=fb8, stream=stream)
-        frame_u8()  # the uint8 variant of the specialized kernel, compiled before any timing
-        sc.jit_wait()
+            def frame_u8():
+                sc.render_device(out=fb8, stream=stream)
+            frame_u8()  # the uint8 variant of the specialized kernel, compiled before any timing
+            sc.jit_wait()
         warm = clock_warmup(full_frame, a.clock_warmup_s, torch.cuda.synchronize)
         for _ in range(a.warmup):
             full_frame()
         torch.cuda.synchronize()
         wall_s = timed(full_frame, a.steps, use_dist)
-        kern_ms = kernel_ms(full_frame, a.steps, stream)  # the render kernel alone, same launches
         kernel = sc.last_kernel
-        clock_warmup(frame_u8, min(0.1, a.clock_warmup_s), torch.cuda.synchronize)  # (its own, right before it)
-        for _ in range(a.warmup):
-            frame_u8()
-        extra["rgb8"] = rgb8_field(frame_u8, a.steps, lambda fn, n: kernel_ms(fn, n, stream), W, H, spp,
-                                   lambda: sc.last_kernel)
+        if a.dump_outputs:
+            dump["framebuffer"] = fb.cpu()
+        if a.full:
+            kern_ms = kernel_ms(full_frame, a.steps, stream)  # the render kernel alone, same launches
+            clock_warmup(frame_u8, min(0.1, a.clock_warmup_s), torch.cuda.synchronize)  # (its own, right before it)
+            for _ in range(a.warmup):
+                frame_u8()
+            extra["rgb8"] = rgb8_field(frame_u8, a.steps, lambda fn, n: kernel_ms(fn, n, stream), W, H, spp,
+                                       lambda: sc.last_kernel)
         rows_frac = 1.0
         scaling, parallelism = "strong", "single GPU"
     else:
@@ -652,45 +699,57 @@ def main():
         own_rows()
         sc.jit_wait()  # (the specialized kernel compiles on a host thread meanwhile)
         warm = clock_warmup(own_rows, a.clock_warmup_s, torch.cuda.synchronize)
-        mg, _ = measure_sharded(sc, rank, world, a.steps, a.warmup, use_dist, dev, stream=stream,
-                                graph=not a.no_graph, collective_at_one=a.pipeline)
-        wall_s = mg.pop("frame_s")
-        # breakdown (outside the timed region): this rank's render alone, fp32 (the kernel
-        # the roofline below prices) and uint8 (the one the frame loop runs), from HIP events
-        rank_fb = torch.empty((max(len(my_rows), 1), W, 3), dtype=torch.float32, device="cuda")
-
-        def fp32_rows():
-            if len(my_rows):
-                rank_render(rank_fb[:len(my_rows)])
-        fp32_rows()  # (its first call may compile the fp32 variant of the specialized kernel)
-        sc.jit_wait()
-        torch.cuda.synchronize()
-        kern_ms = max_over_ranks(kernel_ms(fp32_rows, a.steps, stream), use_dist)
+        if a.full:
+            mg, last_frame = measure_sharded(sc, rank, world, a.steps, a.warmup, use_dist, dev, stream=stream,
+                                             graph=not a.no_graph, collective_at_one=a.pipeline)
+            wall_s = mg.pop("frame_s")
+        else:  # the value's loop alone (sharded_frame)
+            wall_s, last_frame, loop = sharded_frame(sc, rank, world, a.steps, a.warmup, use_dist, dev,
+                                                     stream=stream, graph=not a.no_graph,
+                                                     collective_at_one=a.pipeline, host_issue=False)
+            mg = {"frame_ms": round(wall_s * 1e3 / a.steps, 5), "rows_per_rank": loop["rows_per_rank"],
+                  "partition": loop["partition"], "frame_loop": loop}
         kernel = sc.last_kernel
-        render_ms = max_over_ranks(kernel_ms(own_rows, a.steps, stream), use_dist)
-        mg["render_ms_per_rank"] = round(kern_ms, 5)
-        mg["render_rgb8_ms_per_rank"] = round(render_ms, 5)
-        mg["kernel_rgb8"] = sc.last_kernel
+        if a.dump_outputs and last_frame is not None:
+            dump["frame_rgb8"] = last_frame.cpu()
+        if a.full:
+            # breakdown (outside the timed region): this rank's render alone, fp32 (the kernel
+            # the roofline below prices) and uint8 (the one the frame loop runs), from HIP events
+            rank_fb = torch.empty((max(len(my_rows), 1), W, 3), dtype=torch.float32, device="cuda")
+
+            def fp32_rows():
+                if len(my_rows):
+                    rank_render(rank_fb[:len(my_rows)])
+            fp32_rows()  # (its first call may compile the fp32 variant of the specialized kernel)
+            sc.jit_wait()
+            torch.cuda.synchronize()
+            kern_ms = max_over_ranks(kernel_ms(fp32_rows, a.steps, stream), use_dist)
+            kernel = sc.last_kernel
+            render_ms = max_over_ranks(kernel_ms(own_rows, a.steps, stream), use_dist)
+            mg["render_ms_per_rank"] = round(kern_ms, 5)
+            mg["render_rgb8_ms_per_rank"] = round(render_ms, 5)
+            mg["kernel_rgb8"] = sc.last_kernel
         rows_frac = len(my_rows) / H
         extra["multi_gpu"] = mg
-        # secondary: weak scaling (each rank renders its own whole frame per step)
-        for _ in range(3):
-            full_frame()
-        weak_s = timed(full_frame, a.steps, use_dist)
-        extra["weak_scaling"] = {"Mrays_s": round(world * W * H * spp * a.steps / weak_s / 1e6, 3),
-                                 "ms_per_step": round(weak_s * 1e3 / a.steps, 5),
-                                 "note": "frame-parallel: each rank renders its own whole frame, no collective"}
-        if a.config != SCALING_CONFIG:  # the render-bound scaling config's sharded frame beside it
-            sc2 = make_scene(SCALING_CONFIG)  # (its warm-up frames compile its kernel)
-            extra["scaling_config"] = sharded_config_field(SCALING_CONFIG, sc2, rank, world, min(a.steps, 10), 2,
-                                                           use_dist, dev, stream=stream)
+        if a.full:
+            # secondary: weak scaling (each rank renders its own whole frame per step)
+            for _ in range(3):
+                full_frame()
+            weak_s = timed(full_frame, a.steps, use_dist)
+            extra["weak_scaling"] = {"Mrays_s": round(world * W * H * spp * a.steps / weak_s / 1e6, 3),
+                                     "ms_per_step": round(weak_s * 1e3 / a.steps, 5),
+                                     "note": "frame-parallel: each rank renders its own whole frame, no collective"}
+            if a.config != SCALING_CONFIG:  # the render-bound scaling config's sharded frame beside it
+                sc2 = make_scene(SCALING_CONFIG)  # (its warm-up frames compile its kernel)
+                extra["scaling_config"] = sharded_config_field(SCALING_CONFIG, sc2, rank, world, min(a.steps, 10), 2,
+                                                               use_dist, dev, stream=stream)
         scaling, parallelism = "strong", "rows x %d ranks + one RCCL gather to rank 0 per frame" % world
     ms_per_step = wall_s * 1e3 / a.steps
     value = W * H * spp * a.steps / wall_s / 1e6
 
     if rank == 0:
-        roof = roofline(b_alg * rows_frac, kern_ms, rows_frac,
-                        a.pmc_json or os.path.join(REPO, "profiles", "pmc_%s.json" % a.config))
+        if a.dump_outputs:
+            extra["dumped"] = dump_outputs(a.dump_outputs, dump)
         out = {
             "metric": METRIC if a.config == "tsp1080" else METRIC_OTHER % CONFIGS[a.config][3],
             "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world, "steps": a.steps,
@@ -701,10 +760,13 @@ def main():
             "vs_baseline": None, "dtype": "fp32 vectors + fp64 scalars (reference numerics)", "data": "synthetic",
             "config": {"workload": CONFIGS[a.config][3], "width": W, "height": H, "spp": spp,
                        "frames_per_step": 1, "parallelism": parallelism},
-            "frame_ms": round(kern_ms, 5), "kernel": kernel,
-            "segments_per_frame": segments, "cast_rays_per_frame": cast_rays, "shadow_rays_per_frame": shadow_rays,
-            "roofline": roof,
+            "kernel": kernel, "full": a.full,
         }
+        if a.full:
+            roof = roofline(b_alg * rows_frac, kern_ms, rows_frac,
+                            a.pmc_json or os.path.join(REPO, "profiles", "pmc_%s.json" % a.config))
+            out.update({"frame_ms": round(kern_ms, 5), "segments_per_frame": segments,
+                        "cast_rays_per_frame": cast_rays, "shadow_rays_per_frame": shadow_rays, "roofline": roof})
         out["setup_ms"] = setup
         out.update(extra)
         out.update(cpu)

@@ -13,7 +13,7 @@ for c in ${CONFIGS:-tsp1080 tm1080}; do
   st=50; [ $c = dof4k ] && st=10
   for v in "${VS[@]}"; do
     n=${v%%=*}; f=${v#*=}
-    RTX_JIT_FLAGS="$f" timeout -k 10 120 python bench.py --config $c --steps $st --warmup 3 --no-cpu-baseline \
+    RTX_JIT_FLAGS="$f" timeout -k 10 120 python bench.py --config $c --steps $st --warmup 3 --full --no-cpu-baseline \
       > gpurun_out/abj/${c}_$n.json 2> gpurun_out/abj/${c}_$n.err || { tail -5 gpurun_out/abj/${c}_$n.err; exit 1; }
     python -c "import json;d=json.load(open('gpurun_out/abj/${c}_$n.json'));print('$c $n', d['frame_ms'], d['kernel'])"
   done

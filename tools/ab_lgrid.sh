@@ -8,7 +8,7 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -x -q --timeout 1
 tail -2 gpurun_out/lgrid/tests.log
 run() {  # run TAG CONFIG STEPS [env...]
   local tag=$1 c=$2 st=$3; shift 3
-  env "$@" timeout -k 10 200 python bench.py --config $c --steps $st --warmup 3 --no-cpu-baseline \
+  env "$@" timeout -k 10 200 python bench.py --config $c --steps $st --warmup 3 --full --no-cpu-baseline \
     > gpurun_out/lgrid/$tag.json 2> gpurun_out/lgrid/$tag.err || { tail gpurun_out/lgrid/$tag.err; exit 1; }
   python -c "import json;d=json.load(open('gpurun_out/lgrid/$tag.json'));print('$tag', d['frame_ms'], d['kernel'])"
 }

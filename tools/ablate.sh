@@ -23,7 +23,7 @@ for n in ${VARIANTS:-0 1 2 3}; do
   for c in ${CONFIGS:-tsp1080}; do
     jf_var="JFLAGS_$n"
     env_var="ENV_$n"  # ENV_<name>: extra VAR=value settings for this variant
-    env ${!env_var:-} RTX_JIT_FLAGS="${!jf_var:-}" RTX_LIB_OVERRIDE="$ABL_DIR/librtx_$n.so" timeout -k 10 120 python bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/v${n}_$c.log" 2>&1 || exit 1
+    env ${!env_var:-} RTX_JIT_FLAGS="${!jf_var:-}" RTX_LIB_OVERRIDE="$ABL_DIR/librtx_$n.so" timeout -k 10 120 python bench.py --config $c --steps 20 --warmup 5 --full --no-cpu-baseline > "$OUT/v${n}_$c.log" 2>&1 || exit 1
     echo "variant $n $c $(python3 -c "import json,sys; d=json.loads([l for l in open('$OUT/v${n}_$c.log') if l.startswith('{')][0]); print('frame_ms', d['frame_ms'])")"
   done
 done

@@ -7,8 +7,8 @@
 #
 # tests     python -m pytest tests -m gpu (TESTS="tests/x.py ..." and KEXPR="a or b" narrow it)
 # smoke     __graft_entry__.smoke()
-# bench     the default bench line (N = 1, with CPU baselines unless CPU=0)
-# configs   bench.py --config C for C in CONFIGS (CPU=1 adds the CPU legs to each line)
+# bench     the default bench line with every field (N = 1, --full; with CPU baselines unless CPU=0)
+# configs   bench.py --full --config C for C in CONFIGS (CPU=1 adds the CPU legs to each line)
 # ab        tools/ab_jitflags.sh: VARIANTS="name=jit flags;..." over CONFIGS
 # abl       tools/ab_lib.sh: LIBS="name=_abl/librtx_x.so;name2=default" over CONFIGS (ROUNDS times,
 #           interleaved)
@@ -31,7 +31,7 @@ step() {  # step NAME SECONDS CMD...
   echo "rc=$rc"; tail -3 "$OUT/$name.log"
   return $rc
 }
-cpu_flag() { [ "${CPU:-1}" = 1 ] && echo "--cpu-seconds ${CPU_SECONDS:-10}" || echo "--no-cpu-baseline"; }
+cpu_flag() { [ "${CPU:-1}" = 1 ] && echo "--full --cpu-seconds ${CPU_SECONDS:-10}" || echo "--full --no-cpu-baseline"; }
 for s in ${STEPS:-tests smoke bench rocprof}; do
   case $s in
     tests)
@@ -68,12 +68,12 @@ for s in ${STEPS:-tests smoke bench rocprof}; do
       done ;;
     rocprof)
       step rocprof 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py \
-        --steps 100 --warmup 10 --no-cpu-baseline || exit 1 ;;
+        --steps 100 --warmup 10 --full --no-cpu-baseline || exit 1 ;;
     rocprof_configs)  # rocprofv3 kernel statistics of each config's bench run
       for c in $CFGS; do
         st=100; [ $c = dof4k ] && st=10; [ $c = ns1 ] && st=10; [ $c = ns2 ] && st=3
         step rocprof_$c 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$c" -o run --output-format csv -- python3 bench.py \
-          --config $c --steps $st --warmup 3 --no-cpu-baseline || exit 1
+          --config $c --steps $st --warmup 3 --full --no-cpu-baseline || exit 1
         cp "$OUT/prof_$c/run_kernel_stats.csv" "$OUT/${c}_kernel_stats.csv" 2>/dev/null || \
           find "$OUT/prof_$c" -name '*kernel_stats.csv' -exec cp {} "$OUT/${c}_kernel_stats.csv" \;
       done ;;
@@ -82,7 +82,7 @@ for s in ${STEPS:-tests smoke bench rocprof}; do
         st=200; [ $c = dof4k ] && st=20
         step pipeline1_$c 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
           --master-port 29533 bench.py --gpus 1 --force-dist --pipeline --config $c --steps $st --warmup 5 \
-          --no-cpu-baseline || exit 1
+          --full --no-cpu-baseline || exit 1
         grep '^{' "$OUT/pipeline1_$c.log" > "$OUT/pipeline1_$c.json"
       done ;;
     *) echo "unknown step $s"; exit 2 ;;
