@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define RTX_ABI_VERSION 5
+#define RTX_ABI_VERSION 6
 
 typedef enum rtx_status {
     RTX_OK = 0,
@@ -165,13 +165,17 @@ typedef struct rtx_camera_desc {
     int32_t n_dof, n_aa;
     const float* dof_origins;/* [n_dof][3] _sunflower_spread(dof, position, aperture) */
     const float* aa_origins; /* [n_dof][n_aa][3] _sunflower_spread(aa, dof_origin, 2(dx+dy)) */
-    int32_t n_times;
-    const double* times;     /* [n_times] ViewportCamera.motion_times */
+    int32_t n_times;         /* motion times per frame (the divisor's factor) */
+    const double* times;     /* [n_times] ViewportCamera.motion_times; [n_frames][n_times] for a sequence */
     int32_t jitter;          /* rtx_jitter_mode */
     double jitter_scale;     /* 0.1 * (dx + dy) (scene.py:64) */
     uint64_t seed;           /* RTX_JITTER_PHILOX key */
     const float* noise;      /* RTX_JITTER_REPLAY: host [ncols][height][n_dof][n_aa][3] values of
                                 np.random.rand() in the reference's call order (i, j, dof, aa) */
+    int32_t n_frames;        /* frame sequence (no reference counterpart): 0 or 1 = one window of motion
+                                times, as above; F > 1 (<= 65535, F * n_times <= 2^24) = F windows of
+                                n_times each, which rtx_render_sequence renders by index. Every other
+                                render call uses window 0. Times must be finite. */
 } rtx_camera_desc;
 
 /* Device counters written by rtx_render when counters_dev != NULL (uint64[RTX_COUNTERS]). */
@@ -225,6 +229,22 @@ int rtx_render_frames(rtx_scene* scene, int32_t row0, int32_t nrows, void* out_d
 /* The same for rtx_render_groups / rtx_render_groups_rgb8 (interleaved 8-row groups). */
 int rtx_render_groups_frames(rtx_scene* scene, int32_t phase, int32_t stride, void* out_dev, int32_t rgb8,
                              int32_t nframes, int64_t frame_stride_bytes, uint64_t* counters_dev, void* hip_stream);
+
+/* Frames [frame0, frame0 + nframes) of the camera's sequence (rtx_camera_desc.n_frames windows
+ * of n_times motion times; no reference counterpart) in ONE launch: slot k of out_dev (at
+ * out_dev + k * frame_stride_bytes, as rtx_render_frames) receives what rtx_render /
+ * rtx_render_rgb8 writes for a camera whose motion times are window frame0 + k -- the same
+ * fp32 sums in the same order, divided by n_dof * n_aa * n_times. A moving scene's frames
+ * therefore cost one camera upload, not one each. RTX_ERR_INVALID for a frame range outside
+ * the sequence; the stride rules are rtx_render_frames'. counters_dev accumulates over all
+ * the frames. The culling structures of a sequence camera cover the time range of all its
+ * windows, so a long sequence may render faster in several shorter ones. */
+int rtx_render_sequence(rtx_scene* scene, int32_t row0, int32_t nrows, void* out_dev, int32_t rgb8, int32_t frame0,
+                        int32_t nframes, int64_t frame_stride_bytes, uint64_t* counters_dev, void* hip_stream);
+/* The same for rtx_render_groups / rtx_render_groups_rgb8 (interleaved 8-row groups). */
+int rtx_render_groups_sequence(rtx_scene* scene, int32_t phase, int32_t stride, void* out_dev, int32_t rgb8,
+                               int32_t frame0, int32_t nframes, int64_t frame_stride_bytes, uint64_t* counters_dev,
+                               void* hip_stream);
 
 /* Rows rtx_render_groups writes for an image of `height` rows (-1: bad arguments). */
 int32_t rtx_group_rows(int32_t height, int32_t phase, int32_t stride);

@@ -812,6 +812,20 @@ int convert_scene(const rtx_scene_desc* desc, HostScene& H) {
     return RTX_OK;
 }
 
+// Windows of motion times the camera holds (rtx_camera_desc.n_frames: 0 and 1 both mean one).
+int32_t camera_frames(const rtx_camera_desc* c) { return c->n_frames > 1 ? c->n_frames : 1; }
+
+// Every motion time of the camera as the kernels read it (current_time * speed casts to
+// fp32), [n_frames][n_times]: what is uploaded, and what every time range the host derives
+// from the camera must cover -- the culling structures built for that range (the bins'
+// object masks, the hierarchy bounds, the shadow grids) then hold for each frame of a
+// sequence as they do for each sample of a blurred frame.
+std::vector<float> camera_times(const rtx_camera_desc* c) {
+    std::vector<float> t((size_t)camera_frames(c) * (size_t)c->n_times);
+    for (size_t i = 0; i < t.size(); ++i) t[i] = (float)c->times[i];
+    return t;
+}
+
 // Validates the camera and fills the scalar part of KParams; table pointers are left for
 // the caller (device uploads, or host arrays in the emulation build).
 int convert_camera(const rtx_camera_desc* c, KParams& k) {
@@ -831,6 +845,12 @@ int convert_camera(const rtx_camera_desc* c, KParams& k) {
         return fail(RTX_ERR_INVALID, "rtx_camera_set: non-finite camera basis");
     const int64_t nsamp = (int64_t)c->n_dof * c->n_aa;
     if (nsamp * c->n_times > ((int64_t)1 << 24)) return fail(RTX_ERR_INVALID, "rtx_camera_set: too many samples per pixel");
+    if (c->n_frames < 0 || c->n_frames > 65535)
+        return fail(RTX_ERR_INVALID, "rtx_camera_set: a sequence holds 1 <= n_frames <= 65535 windows");
+    if ((int64_t)camera_frames(c) * c->n_times > ((int64_t)1 << 24))  // (the table's indices are int32)
+        return fail(RTX_ERR_INVALID, "rtx_camera_set: more than 2^24 motion times in the sequence");
+    for (int64_t i = 0, n = (int64_t)camera_frames(c) * c->n_times; i < n; ++i)
+        if (!std::isfinite(c->times[i])) return fail(RTX_ERR_INVALID, "rtx_camera_set: non-finite motion time");
     std::memset(&k, 0, sizeof(k));
     set3(k.pos, c->position);
     set3(k.u, c->u);
@@ -844,6 +864,7 @@ int convert_camera(const rtx_camera_desc* c, KParams& k) {
     k.jscale = (float)c->jitter_scale;
     k.width = c->width; k.height = c->height; k.col0 = c->col0; k.ncols = c->ncols;
     k.n_dof = c->n_dof; k.n_aa = c->n_aa; k.n_times = c->n_times; k.jitter = c->jitter;
+    k.n_frames = camera_frames(c);
     k.seed_lo = (uint32_t)c->seed; k.seed_hi = (uint32_t)(c->seed >> 32);
     return RTX_OK;
 }
@@ -1033,9 +1054,9 @@ bool primary_bins(const HostScene& H, const rtx_camera_desc* c, const std::vecto
     const Rect all{0, bins_x - 1, 0, bins_y - 1};
     // moving objects: moved() = fl32(p + speed * time) over the frame's times, padded
     double tlo = INFINITY, thi = -INFINITY;
-    for (int32_t i = 0; i < c->n_times; ++i) {
-        tlo = std::min(tlo, (double)(float)c->times[i]);
-        thi = std::max(thi, (double)(float)c->times[i]);
+    for (float t : camera_times(c)) {  // (every frame of a sequence)
+        tlo = std::min(tlo, (double)t);
+        thi = std::max(thi, (double)t);
     }
     auto sweep = [&](const DObj& ob, double* lo, double* hi) {
         if (!ob.has_speed) return;
@@ -1843,6 +1864,8 @@ void jit_fixed_opts(const SceneView& v, const KParams& kp, const SceneTraits& tr
           "-DRTX_FIXED_POWBITS=" + std::to_string(v.pow_bits)})
         opts.push_back(o);
     if (tr.uniform_hard >= 0) opts.push_back("-DRTX_FIXED_HARD=" + std::to_string(tr.uniform_hard));
+    // a sequence camera's kernels index the motion times by frame (rtx_kernels.h time_base)
+    if (kp.n_frames > 1) opts.push_back("-DRTX_SEQUENCE=1");
     if (!camera) return;
     for (const std::string& o :
          {std::string("-DRTX_FIXED_SAMPLES"), "-DRTX_FIXED_NDOF=" + std::to_string(kp.n_dof),
@@ -2846,8 +2869,7 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
     if (rc) return rc;
     free_camera(s);
     const size_t nsamp = (size_t)c->n_dof * c->n_aa;
-    std::vector<float> times(c->n_times);
-    for (int i = 0; i < c->n_times; ++i) times[i] = (float)c->times[i];  // current_time * speed casts to fp32
+    const std::vector<float> times = camera_times(c);
     const auto mm = std::minmax_element(times.begin(), times.end());
     const double omax = camera_origin_bound(c);
     k.S = s->view;
@@ -3084,8 +3106,23 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
 namespace {
 int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, bool out8, int32_t nframes = 1);
 
+// frame0 >= 0 (rtx_render_sequence): slot k renders window frame0 + k of the camera's
+// sequence; frame0 < 0 (every other call): nframes copies of window 0.
+int sequence_range(const char* fn, const rtx_scene* s, int32_t frame0, int32_t nframes, Launch& L) {
+    L.tbase = 0;
+    L.tstep = 0;
+    if (frame0 < 0) return RTX_OK;
+    if ((int64_t)frame0 + nframes > s->kp.n_frames)
+        return fail(RTX_ERR_INVALID, std::string(fn) + ": frames [" + std::to_string(frame0) + ", " +
+                                         std::to_string((int64_t)frame0 + nframes) + ") outside the camera's sequence of " +
+                                         std::to_string(s->kp.n_frames));
+    L.tbase = frame0 * s->kp.n_times;
+    L.tstep = s->kp.n_times;
+    return RTX_OK;
+}
+
 int render_rows(const char* fn, rtx_scene* s, int32_t row0, int32_t nrows, void* out_dev, uint64_t* counters_dev,
-                void* stream, bool out8, int32_t nframes = 1, int64_t fstride = 0) {
+                void* stream, bool out8, int32_t nframes = 1, int64_t fstride = 0, int32_t frame0 = -1) {
     if (!s) return fail(RTX_ERR_INVALID, std::string(fn) + ": null scene");
     if (!s->cam_set) return fail(RTX_ERR_STATE, std::string(fn) + ": rtx_camera_set was not called");
     if (row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > s->kp.height)
@@ -3093,9 +3130,10 @@ int render_rows(const char* fn, rtx_scene* s, int32_t row0, int32_t nrows, void*
     const int64_t block_bytes = (int64_t)nrows * s->kp.ncols * 3 * (out8 ? 1 : 4);
     if (nframes < 1 || nframes > 65535 || (nframes > 1 && fstride < block_bytes) || (!out8 && fstride % 4))
         return fail(RTX_ERR_INVALID, std::string(fn) + ": need 1 <= nframes <= 65535 and frames that do not overlap");
+    Launch L;
+    if (int rc = sequence_range(fn, s, frame0, nframes, L)) return rc;
     if (nrows == 0) return RTX_OK;
     if (!out_dev) return fail(RTX_ERR_INVALID, std::string(fn) + ": null framebuffer");
-    Launch L;
     L.fb = static_cast<float*>(out_dev);
     L.row0 = row0;
     L.nrows = nrows;
@@ -3106,7 +3144,7 @@ int render_rows(const char* fn, rtx_scene* s, int32_t row0, int32_t nrows, void*
 }
 
 int render_groups(const char* fn, rtx_scene* s, int32_t phase, int32_t stride, void* out_dev, uint64_t* counters_dev,
-                  void* stream, bool out8, int32_t nframes = 1, int64_t fstride = 0) {
+                  void* stream, bool out8, int32_t nframes = 1, int64_t fstride = 0, int32_t frame0 = -1) {
     if (!s) return fail(RTX_ERR_INVALID, std::string(fn) + ": null scene");
     if (!s->cam_set) return fail(RTX_ERR_STATE, std::string(fn) + ": rtx_camera_set was not called");
     const int32_t nrows = rtx_group_rows(s->kp.height, phase, stride);
@@ -3114,9 +3152,10 @@ int render_groups(const char* fn, rtx_scene* s, int32_t phase, int32_t stride, v
     const int64_t block_bytes = (int64_t)nrows * s->kp.ncols * 3 * (out8 ? 1 : 4);
     if (nframes < 1 || nframes > 65535 || (nframes > 1 && fstride < block_bytes) || (!out8 && fstride % 4))
         return fail(RTX_ERR_INVALID, std::string(fn) + ": need 1 <= nframes <= 65535 and frames that do not overlap");
+    Launch L;
+    if (int rc = sequence_range(fn, s, frame0, nframes, L)) return rc;
     if (nrows == 0) return RTX_OK;
     if (!out_dev) return fail(RTX_ERR_INVALID, std::string(fn) + ": null framebuffer");
-    Launch L;
     L.fb = static_cast<float*>(out_dev);
     L.row0 = 0;
     L.nrows = nrows;
@@ -3146,6 +3185,21 @@ int rtx_render_groups_frames(rtx_scene* s, int32_t phase, int32_t stride, void* 
                              int32_t nframes, int64_t frame_stride_bytes, uint64_t* counters_dev, void* stream) {
     return render_groups("rtx_render_groups_frames", s, phase, stride, out_dev, counters_dev, stream, rgb8 != 0,
                          nframes, frame_stride_bytes);
+}
+
+int rtx_render_sequence(rtx_scene* s, int32_t row0, int32_t nrows, void* out_dev, int32_t rgb8, int32_t frame0,
+                        int32_t nframes, int64_t frame_stride_bytes, uint64_t* counters_dev, void* stream) {
+    if (frame0 < 0) return fail(RTX_ERR_INVALID, "rtx_render_sequence: frame0 < 0");
+    return render_rows("rtx_render_sequence", s, row0, nrows, out_dev, counters_dev, stream, rgb8 != 0, nframes,
+                       frame_stride_bytes, frame0);
+}
+
+int rtx_render_groups_sequence(rtx_scene* s, int32_t phase, int32_t stride, void* out_dev, int32_t rgb8,
+                               int32_t frame0, int32_t nframes, int64_t frame_stride_bytes, uint64_t* counters_dev,
+                               void* stream) {
+    if (frame0 < 0) return fail(RTX_ERR_INVALID, "rtx_render_groups_sequence: frame0 < 0");
+    return render_groups("rtx_render_groups_sequence", s, phase, stride, out_dev, counters_dev, stream, rgb8 != 0,
+                         nframes, frame_stride_bytes, frame0);
 }
 
 int32_t rtx_group_rows(int32_t height, int32_t phase, int32_t stride) {
@@ -3391,6 +3445,7 @@ int render_split(rtx_scene* s, Launch L, const KParams* kp, size_t hbytes, hipSt
         Launch Lc = L;
         Lc.fb = reinterpret_cast<float*>(base + f * L.fstride);
         Lc.fstride = 0;
+        Lc.tbase = L.tbase + f * L.tstep;  // (one frame per iteration: its window of a sequence)
         Lc.redo = RedoList{nullptr, nullptr, nullptr};
         RTX_HIP(hipMemsetAsync(s->d_split_count, 0, 2 * sizeof(unsigned int) * nchunk, st));
         int64_t c = 0;
@@ -3501,7 +3556,8 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
                            L.gstride == 0;
         // (a captured launch neither measures nor sorts: its replays run later, and the
         // schedule's state machine follows eager frames only)
-        const bool capturing = whole && stream_capturing(st);
+        // (nor does a sequence launch: its frames differ in cost)
+        const bool capturing = whole && (L.tstep != 0 || stream_capturing(st));
         if (whole && !capturing) {
             if (int rc = tile_schedule(s, st, (uint32_t)rs.block / 64)) return rc;
             L.tlog = s->tile_sched == 1;
@@ -3524,9 +3580,11 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
     if (out8 && nframes > 1) {  // generic kernels: the uint8 fallback below, one frame at a time
         char* base = reinterpret_cast<char*>(L.fb);
         const int64_t fstride = L.fstride;
+        const int32_t tbase = L.tbase;
         L.fstride = 0;
         for (int32_t f = 0; f < nframes; ++f) {
             L.fb = reinterpret_cast<float*>(base + f * fstride);
+            L.tbase = tbase + f * L.tstep;  // (blockIdx.y is 0: the frame's window of a sequence)
             if (int rc = render_launch(s, L, counters_dev, stream, true, 1)) return rc;
         }
         return RTX_OK;

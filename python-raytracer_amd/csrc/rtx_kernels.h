@@ -20,11 +20,12 @@ struct KParams {
     cptr<float> ys;
     cptr<float> dof_o;   // [n_dof][3]
     cptr<float> aa_o;    // [n_dof][n_aa][3]
-    cptr<float> times;   // [n_times] fp32
+    cptr<float> times;   // [n_times] fp32; a sequence camera's [n_frames][n_times] (time_base)
     cptr<float> noise;   // replay jitter
     float pos[4], u[4], v[4], dw[4];
     float focal, divisor, jscale, inv_divisor;
-    int32_t div_pow2, pad0, pad1, pad2;
+    // n_frames: windows in `times` (host bookkeeping; the kernels index by Launch::tbase / tstep)
+    int32_t div_pow2, n_frames, pad1, pad2;
     int32_t width, height, col0, ncols;
     int32_t n_dof, n_aa, n_times, jitter;
     uint32_t seed_lo, seed_hi;
@@ -216,10 +217,11 @@ RTX_HD SceneView sample_scene(const SceneView& S0) {
 }
 
 // scene.py:47-79 for pixel p of the output block (host/device: the tests-only host
-// emulation runs the same body).
+// emulation runs the same body). tb: the index in P.times of the frame's window of motion
+// times (time_base below; 0 for every camera without a sequence).
 template <bool MESH, bool SEC, bool X, bool COUNT, bool JIT>
 RTX_HD void render_pixel(const KParams& P, float* fb, int32_t row0, int32_t rr, int32_t cc, Tally& tl,
-                         const FrameStack& fs, const HStack& hs, int32_t bin = -1) {
+                         const FrameStack& fs, const HStack& hs, int32_t bin = -1, int32_t tb = 0) {
     if (RTX_PROBE(14)) {  // cost probe only: store a constant (launch + framebuffer write)
         const int64_t p = (int64_t)rr * P.ncols + cc;
         put_channel(fb, 3 * p, 0.5f); put_channel(fb, 3 * p + 1, 0.25f); put_channel(fb, 3 * p + 2, 0.125f);
@@ -269,7 +271,7 @@ RTX_HD void render_pixel(const KParams& P, float* fb, int32_t row0, int32_t rr, 
             const f3 o = sample_origin<JIT>(P, cc, j, kd, ka, philox ? &jr : nullptr);
 #pragma unroll 1
             for (int kt = 0; kt < RTX_NTIMES(P); ++kt)
-                colour = add(colour, cast_ray<MESH, SEC, X, COUNT>(sample_scene<X>(P.S), o, ddir, P.times[kt], tl, fs, hs,
+                colour = add(colour, cast_ray<MESH, SEC, X, COUNT>(sample_scene<X>(P.S), o, ddir, P.times[tb + kt], tl, fs, hs,
                                                                    bin, primp, blane));
         }
     }
@@ -308,6 +310,7 @@ RTX_HD uint2 mesh_chunk(const KParams& P, int32_t bin, int32_t c, int lane) {
     const f3 o = ld3(P.aa_o);  // scene.py:60-61 (one sample, no jitter)
     const int32_t oi = S.n_plane + S.n_sphere + S.n_box;  // the scene's one top-level mesh
     const DObj ob = S.objs[oi];
+    // (times[0] whatever the frame of a sequence: the chunks test the mesh, which does not move)
     const float time = P.times[0];
     const RayInv ri = ray_inv(o, d);
     Hit h{INFINITY, -1, 0};
@@ -365,7 +368,7 @@ __device__ __forceinline__ uint2 mesh_chunk_lds(const KParams& P, int32_t bin, i
     const int j = P.height - 1 - (active ? row : 0);
     const f3 d = normalize(sub(pixel_focal(P, active ? cc : 0, j), ld3(P.dof_o)));  // scene.py:58
     const f3 o = ld3(P.aa_o);  // scene.py:60-61 (one sample, no jitter)
-    const float time = P.times[0];
+    const float time = P.times[0];  // (as mesh_chunk: static geometry)
     const RayInv ri = ray_inv(o, d);
     Hit h{INFINITY, -1, 0};
     for (int i = 0; i < n; ++i) {
@@ -405,6 +408,10 @@ struct Launch {
     int32_t tperm;  // RTX_TILE_SCHED kernels: 1 = dispatch a whole frame's tiles by P.tile_perm
     int32_t tlog;   // RTX_TILE_SCHED kernels: 1 = record each wave's duration in P.tile_time
     int32_t xcd;    // 1 = XCD-aware block order (xcd_block; tile-mapped render_body)
+    // rtx_render_sequence: frame y of the launch (blockIdx.y) takes its motion times from
+    // P.times[tbase + y * tstep + kt]. tstep = 0 (every other call): the frames are copies
+    // of window tbase / n_times (rtx_render_frames); both 0 for a camera without a sequence.
+    int32_t tbase, tstep;
     // render_body_spp as the split passes' fallback (rtx_split.h): render only the listed
     // blocks (chains that found the record pool full), pixels from pix0 on
     RedoList redo;
@@ -413,6 +420,30 @@ struct Launch {
 // This block's framebuffer (frame blockIdx.y of a batched launch; the only frame otherwise).
 __device__ __forceinline__ float* frame_fb(const Launch& L) {
     return reinterpret_cast<float*>(reinterpret_cast<char*>(L.fb) + (int64_t)blockIdx.y * L.fstride);
+}
+
+// The frame-dependent window of motion times (rtx_render_sequence). Scene-specialized
+// kernels carry this arithmetic only when their camera holds a sequence (RTX_SEQUENCE=1 in
+// their options): for every other camera they are what they were without it. The
+// precompiled generic kernels take the run-time fields.
+#ifndef RTX_SEQUENCE
+#if defined(__HIPCC_RTC__)
+#define RTX_SEQUENCE 0
+#else
+#define RTX_SEQUENCE 1
+#endif
+#endif
+
+// Index in P.times of this block's window (host: Launch::tbase, one frame per call).
+RTX_HD int32_t time_base(const Launch& L) {
+#if RTX_SEQUENCE && defined(__HIP_DEVICE_COMPILE__)
+    return L.tbase + (int32_t)blockIdx.y * L.tstep;
+#elif RTX_SEQUENCE
+    return L.tbase;
+#else
+    (void)L;
+    return 0;
+#endif
 }
 
 // Image row (row 0 = top) of block row rr.
@@ -605,6 +636,7 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
     const FrameStack fs{frames + threadIdx.x, B};
     const HStack hs{hstack + threadIdx.x, B};
     bool any_active = false;
+    const int32_t tb = time_base(L);
 #if RTX_TILE_SCHED && defined(__HIP_DEVICE_COMPILE__)
     static_assert(RTX_TILE == 1 && RTX_PPL == 1, "the tile schedule orders whole 8x8 tiles");
     const unsigned long long tclk0 = L.tlog ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -622,7 +654,8 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
         const int32_t bin = RTX_TILE == 1 ? primary_bin(Pp->S, image_row(L, px.r & ~7), px.c & ~7) : -1;
         // render_pixel's image row is row0 + rr: pass the image row of px.r as that sum
         if (active)
-            render_pixel<MESH, SEC, X, COUNT, JIT>(*Pp, frame_fb(L), image_row(L, px.r) - px.r, px.r, px.c, tl, fs, hs, bin);
+            render_pixel<MESH, SEC, X, COUNT, JIT>(*Pp, frame_fb(L), image_row(L, px.r) - px.r, px.r, px.c, tl, fs, hs, bin,
+                                                   tb);
     }
     flush_tally<COUNT>(tl, L.counters, any_active);
 #if RTX_TILE_SCHED && defined(__HIP_DEVICE_COMPILE__)
@@ -673,6 +706,7 @@ __device__ __forceinline__ void render_block_spp(const KParams* __restrict__ Pp,
     const int64_t npix = (int64_t)L.nrows * ncols;
     const int64_t pix0 = L.pix0 + blk * PPB;
     const int tid = threadIdx.x;
+    const int32_t tb = time_base(L);
     float acc = 0.0f;  // rounds > 1 (one pixel per block): lane ch < 3 sums channel ch
     for (int rd = 0; rd < rounds; ++rd) {
         const int flat = rd * B + tid;  // the block's sample index
@@ -691,7 +725,7 @@ __device__ __forceinline__ void render_block_spp(const KParams* __restrict__ Pp,
             const f3 focal = pixel_focal(P, cc, j);
             const f3 ddir = normalize(sub(focal, ld3(P.dof_o + 3 * kd)));  // scene.py:58
             const f3 o = sample_origin<JIT>(P, cc, j, kd, ka);
-            c = cast_ray<MESH, SEC, X, COUNT>(P.S, o, ddir, P.times[kt], tl, fs, hs);
+            c = cast_ray<MESH, SEC, X, COUNT>(P.S, o, ddir, P.times[tb + kt], tl, fs, hs);
         }
         sbuf[tid] = c.x;
         sbuf[B + tid] = c.y;

@@ -114,7 +114,7 @@ RTX_HD void trace_sample(const KParams& P, const Launch& L, const SplitBuf& sb, 
     const SampleIx x = sample_ix(P, L, q, Sn, nt, na);
     f3 d = sample_dir(P, x);
     f3 o = sample_origin<JIT>(P, x.cc, x.j, x.kd, x.ka);
-    const float time = P.times[x.kt];
+    const float time = P.times[time_base(L) + x.kt];  // (the host launches one frame of a sequence at a time)
     // the primary-ray bin of the wave's pixels when they share one (rtx_api.hip primary_bins)
     int32_t bin = -1;
 #if !(defined(RTX_PRIMARY_BINS) && !RTX_PRIMARY_BINS)
@@ -238,7 +238,7 @@ RTX_HD f3 shade_sample(const KParams& P, const Launch& L, const SplitBuf& sb, in
     const int nt = RTX_NTIMES(P), na = RTX_NAA(P);
     const int Sn = RTX_NDOF(P) * na * nt;
     const SampleIx x = sample_ix(P, L, q, Sn, nt, na);
-    const float time = P.times[x.kt];
+    const float time = P.times[time_base(L) + x.kt];
     f3 d = sample_dir(P, x);
     int nfr = 0;  // frames on the stack (levels whose colour blends with a child's)
     bool in_shape = false;
@@ -340,7 +340,7 @@ __device__ __forceinline__ void split_shadow(const KParams* __restrict__ Pp, con
         any = true;
         if (hit) {
             const f3 pos = mk(sb.f(kSpPx)[r], sb.f(kSpPy)[r], sb.f(kSpPz)[r]);
-            const float time = Pp->times[(meta >> 2) & (kSpMaxTimes - 1)];
+            const float time = Pp->times[time_base(L) + (int32_t)((meta >> 2) & (kSpMaxTimes - 1))];
             sb.u(kSpOcc)[r] = shadow_mask<MESH, COUNT>(S, pos, time, tl, hs);
         }
     }

@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(HERE, "_lib", "librtx.so")
 # Experiment builds (tools/ablate.sh) point this at another build of the same HIP source.
 _BUILT_PATH = LIB_PATH
 LIB_PATH = os.environ.get("RTX_LIB_OVERRIDE", LIB_PATH)
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 RTX_OK, RTX_ERR_INVALID, RTX_ERR_HIP, RTX_ERR_UNSUPPORTED, RTX_ERR_STATE = 0, -1, -2, -3, -4
 RTX_SPHERE, RTX_PLANE, RTX_BOX, RTX_MESH, RTX_NODE = 0, 1, 2, 3, 4
@@ -74,7 +74,8 @@ class rtx_camera_desc(C.Structure):
                 ("xs", _pf), ("ys", _pf), ("position", _f3), ("u", _f3), ("v", _f3), ("w", _f3),
                 ("d", C.c_double), ("focal_length", C.c_double), ("n_dof", C.c_int32), ("n_aa", C.c_int32),
                 ("dof_origins", _pf), ("aa_origins", _pf), ("n_times", C.c_int32), ("times", _pd),
-                ("jitter", C.c_int32), ("jitter_scale", C.c_double), ("seed", C.c_uint64), ("noise", _pf)]
+                ("jitter", C.c_int32), ("jitter_scale", C.c_double), ("seed", C.c_uint64), ("noise", _pf),
+                ("n_frames", C.c_int32)]
 
 
 class RtxError(RuntimeError):
@@ -90,7 +91,7 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_scene_create", "rtx_scene_d
            "rtx_render", "rtx_render_groups", "rtx_group_rows", "rtx_intersect", "rtx_occluded", "rtx_fb_to_rgb8",
            "rtx_render_rgb8", "rtx_render_groups_rgb8", "rtx_last_kernel", "rtx_render_frames",
            "rtx_render_groups_frames", "rtx_jit_modules", "rtx_set_option", "rtx_get_option", "rtx_option_name",
-           "rtx_graph_launch", "rtx_jit_wait"]
+           "rtx_graph_launch", "rtx_jit_wait", "rtx_render_sequence", "rtx_render_groups_sequence"]
 
 
 def load():
@@ -116,6 +117,9 @@ def load():
         lib.rtx_render_frames.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp]
         lib.rtx_render_groups_frames.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int64, vp,
                                                  vp]
+        if hasattr(lib, "rtx_render_sequence"):
+            for f in (lib.rtx_render_sequence, lib.rtx_render_groups_sequence):
+                f.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, vp]
         lib.rtx_group_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.rtx_group_rows.restype = C.c_int32
         lib.rtx_intersect.argtypes = [vp, C.c_int64, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]

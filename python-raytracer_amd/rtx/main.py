@@ -7,6 +7,15 @@ Full render: rot90 + truncating uint8 conversion + PNG (main.py:29-34; the viewe
 float64 strip (main.py:26-28), for rtx.glue. Extensions: --resolution W H and --spp AA [DOF]
 edit the scene like the bench configs; --distributed renders row blocks on every rank
 of a torch.distributed job and gathers the frame to rank 0 (render.nu's role).
+
+    python -m rtx.main --infile S.json --frames N [--time-range T0 T1]
+                       [--shutter S --shutter-samples M] --outfile out.png
+
+A frame sequence of a moving scene (no reference counterpart): N frames opening at equal
+steps over [T0, T1) -- default 0 .. the scene's last motion time -- each blurred over S
+time units with M samples (default: one time per frame), rendered by
+Scene.render_sequence in batches and written as out_0000.png, out_0001.png, ... (or through
+a %d pattern in the name, e.g. frame%03d.png).
 """
 import argparse
 import json
@@ -25,7 +34,59 @@ def parse(argv=None):
     p.add_argument("--spp", type=int, nargs="+", default=None, help="AA samples [DOF samples]")
     p.add_argument("--distributed", action="store_true")
     p.add_argument("--quiet", action="store_true")
-    return p.parse_args(argv)
+    p.add_argument("--frames", type=int, default=None, help="render a sequence of this many frames")
+    p.add_argument("--time-range", type=float, nargs=2, default=None, metavar=("T0", "T1"),
+                   help="motion times the sequence spans (default: 0 .. the scene's last motion time)")
+    p.add_argument("--shutter", type=float, default=0.0, help="time each frame is blurred over")
+    p.add_argument("--shutter-samples", type=int, default=1, help="motion times per frame")
+    args = p.parse_args(argv)
+    if args.frames is not None:
+        if args.distributed or args.subimage is not None or args.tasks is not None:
+            p.error("--frames renders whole frames on one GPU: it cannot be combined with --distributed or "
+                    "--subimage / --tasks")
+        if args.frames < 1 or args.shutter_samples < 1:
+            p.error("--frames and --shutter-samples must be >= 1")
+        try:
+            frame_names(args.outfile, 1)
+        except (TypeError, ValueError):
+            p.error("--outfile may hold one integer pattern such as %%04d, not %r" % args.outfile)
+    elif args.time_range is not None or args.shutter != 0.0 or args.shutter_samples != 1:
+        p.error("--time-range, --shutter and --shutter-samples need --frames")
+    return args
+
+
+def frame_names(outfile, frames):
+    """The sequence's file names: ``outfile`` % f when it holds a pattern such as %04d, else
+    the frame number (at least four digits) goes before the extension: out.png -> out_0000.png."""
+    if "%" in outfile:
+        return [outfile % f for f in range(frames)]
+    root, ext = os.path.splitext(outfile)
+    return ["%s_%04d%s" % (root, f, ext) for f in range(frames)]
+
+
+# Frames per camera upload and launch of a CLI sequence: the frames of a batch wait on the
+# device as uint8 (this many bytes at most), and a batch's culling structures cover only its
+# own time range.
+SEQUENCE_BATCH_BYTES = 256 << 20
+SEQUENCE_BATCH_FRAMES = 64
+
+
+def render_frames_to_files(sc, args):
+    from PIL import Image
+    from .scene import frame_windows
+    t0, t1 = args.time_range if args.time_range is not None else (0.0, float(sc.vc.motion_times[-1]))
+    windows = frame_windows(t0, t1, args.frames, args.shutter, args.shutter_samples)
+    names = frame_names(args.outfile, args.frames)
+    batch = max(1, min(SEQUENCE_BATCH_FRAMES, SEQUENCE_BATCH_BYTES // (sc.vc.width * sc.vc.height * 3)))
+    for f0 in range(0, args.frames, batch):
+        rgb = sc.render_sequence(windows[f0:f0 + batch], rgb8=True).cpu().numpy()
+        # the scene-specialized kernels compile on a host thread while the generic ones render
+        # (option jit_async): wait for them, so that the later batches run them and a short
+        # sequence does not end the process with a compile still running
+        sc.jit_wait()
+        for k, img in enumerate(rgb):
+            Image.fromarray(img).save(names[f0 + k])
+    return names
 
 
 def _scene(args):
@@ -62,6 +123,9 @@ def main(argv=None):
         dist.destroy_process_group()
         return
     full_scene = _scene(args)
+    if args.frames is not None:
+        render_frames_to_files(full_scene, args)
+        return
     if args.subimage is not None and args.tasks is not None:
         image = full_scene.render(args.subimage, args.tasks)
         numpy.save(args.outfile, image)

@@ -11,6 +11,7 @@ motion times) and moves buffers.
 import ctypes as C
 import hashlib
 import itertools
+import math
 
 import numpy as np
 import torch
@@ -77,6 +78,44 @@ def fb_to_rgb8(fb, out=None, stream=None):
     N.call("rtx_fb_to_rgb8", C.c_void_p(fb.data_ptr()), C.c_void_p(out.data_ptr()), int(fb.numel()),
            C.c_void_p(st.cuda_stream))
     return out
+
+
+def frame_windows(start, stop, frames, shutter=0.0, samples=1, final=0):
+    """The motion-time windows of ``frames`` frames over [start, stop), for
+    Scene.render_sequence: frame f opens at t_f = start + (stop - start) / frames * f, and
+    its window is ViewportCamera.set_motion's rule shifted to t_f --
+    [t_f + shutter / samples * i for i in range(samples)] + [t_f + shutter] * final
+    (shutter 0.0, samples 1: the single time t_f). Python float arithmetic throughout."""
+    frames, samples, final = int(frames), int(samples), int(final)
+    if frames < 1 or samples < 0 or final < 0 or samples + final < 1:
+        raise ValueError("frame_windows needs frames >= 1 and samples + final >= 1 (none negative)")
+    start, stop, shutter = float(start), float(stop), float(shutter)
+    step = (stop - start) / frames
+    dt = shutter / samples if samples else 0.0
+    out = []
+    for f in range(frames):
+        t = start + step * f
+        out.append([t + dt * i for i in range(samples)] + [t + shutter] * final)
+    return sequence_windows(out)
+
+
+def sequence_windows(windows):
+    """``windows`` as a list of F >= 1 lists of T >= 1 Python floats (a flat sequence of
+    numbers: T = 1). ValueError for an empty, ragged or non-finite sequence."""
+    try:
+        rows = list(windows)
+        if rows and all(np.ndim(w) == 0 for w in rows):
+            rows = [[w] for w in rows]
+        rows = [[float(t) for t in w] for w in rows]
+    except TypeError:
+        raise ValueError("windows must be a sequence of equal-length sequences of motion times") from None
+    if not rows or not rows[0]:
+        raise ValueError("a frame sequence needs at least one window of at least one motion time")
+    if any(len(w) != len(rows[0]) for w in rows):
+        raise ValueError("every window of a frame sequence holds the same number of motion times")
+    if not all(math.isfinite(t) for w in rows for t in w):
+        raise ValueError("motion times must be finite")
+    return rows
 
 
 _GENERATION = itertools.count(1)
@@ -204,8 +243,10 @@ class Scene:
         return self._native
 
     # ------------------------------------------------------------------ camera tables
-    def camera_tables(self, subimage=0, tasks=1):
-        """The reference's per-frame scalars (scene.py:36-45, :48-61), evaluated on the host."""
+    def camera_tables(self, subimage=0, tasks=1, windows=None):
+        """The reference's per-frame scalars (scene.py:36-45, :48-61), evaluated on the host.
+        ``windows`` (a frame sequence, sequence_windows): the motion times are its F windows
+        of T times, [F][T] flattened, in place of vc.motion_times."""
         vc = self.vc
         col0, ncols = strip_columns(vc.width, subimage, tasks)
         dx = (vc.right - vc.left) / vc.width
@@ -218,12 +259,17 @@ class Scene:
         aa = sunflower_many(self.samples, dof, 2 * (dx + dy))
         return dict(col0=col0, ncols=ncols, xs=xs.astype(np.float32), ys=ys.astype(np.float32),
                     dof=np.ascontiguousarray(dof), aa=np.ascontiguousarray(aa),
-                    times=np.asarray(vc.motion_times, np.float64), jscale=0.1 * (dx + dy))
+                    times=np.asarray(vc.motion_times if windows is None else windows, np.float64).ravel(),
+                    n_times=len(vc.motion_times) if windows is None else len(windows[0]),
+                    n_frames=0 if windows is None else len(windows), jscale=0.1 * (dx + dy))
 
-    def camera_desc(self, subimage=0, tasks=1):
+    def camera_desc(self, subimage=0, tasks=1, windows=None):
         """rtx_camera_desc for the strip; returns (desc, tables). The tables own the
-        memory the descriptor points at: keep them alive while the descriptor is used."""
-        t = self.camera_tables(subimage, tasks)
+        memory the descriptor points at: keep them alive while the descriptor is used.
+        ``windows``: a frame sequence's camera (n_frames windows of n_times motion times)."""
+        if windows is not None:
+            windows = sequence_windows(windows)
+        t = self.camera_tables(subimage, tasks, windows)
         vc = self.vc
         d = N.rtx_camera_desc()
         d.width, d.height, d.col0, d.ncols = vc.width, vc.height, t["col0"], t["ncols"]
@@ -232,7 +278,7 @@ class Scene:
         d.d, d.focal_length = float(vc.d), float(vc.focal_length)
         d.n_dof, d.n_aa = vc.dof_samples, self.samples
         d.dof_origins, d.aa_origins = _ptr(t["dof"], C.c_float), _ptr(t["aa"], C.c_float)
-        d.n_times, d.times = len(t["times"]), _ptr(t["times"], C.c_double)
+        d.n_times, d.times, d.n_frames = t["n_times"], _ptr(t["times"], C.c_double), t["n_frames"]
         d.jitter_scale, d.seed = float(t["jscale"]), int(self.seed) & 0xFFFFFFFFFFFFFFFF
         if not self.jitter:
             d.jitter = N.RTX_JITTER_OFF
@@ -273,12 +319,14 @@ class Scene:
             self._noise_src, self._noise_digest = src, (a.size, hashlib.blake2b(a.tobytes(), digest_size=16).digest())
         return self._noise_digest
 
-    def _set_camera(self, subimage, tasks):
+    def _set_camera(self, subimage, tasks, windows=None):
         key = self._camera_key(subimage, tasks)
+        if windows is not None:  # the sequence is part of the key: render() uploads the ordinary camera again
+            key += (("sequence", len(windows[0]), tuple(t for w in windows for t in w)),)
         nat = self.native()
         if self._cam_key == key:
             return self._cam_info
-        d, t = self.camera_desc(subimage, tasks)
+        d, t = self.camera_desc(subimage, tasks, windows)
         N.call("rtx_camera_set", nat.h, C.byref(d))
         self._cam_key = key
         self._cam_info = t
@@ -344,6 +392,60 @@ class Scene:
         fn, a, b = ("rtx_render_frames", row0, nrows) if groups is None else ("rtx_render_groups_frames",) + tuple(groups)
         N.call(fn, self._native.h, int(a), int(b), C.c_void_p(out.data_ptr()), int(out.dtype == torch.uint8),
                int(out.shape[0]), int(out.stride(0) * out.element_size()), None, C.c_void_p(st.cuda_stream))
+        return out
+
+    def render_sequence(self, windows, out=None, row0=0, nrows=None, groups=None, counters=None, stream=None,
+                        rgb8=False, batch=None, frames=None):
+        """A frame sequence of a moving scene: frame f is what render_device renders after
+        ``vc.motion_times = windows[f]``, bit for bit, without a camera upload per frame.
+        ``windows`` holds F equal-length lists of motion times (rtx.frame_windows makes
+        them; a flat list of numbers: one time per frame). Returns a CUDA tensor
+        [F, nrows, W, 3], float32 or (rgb8=True, or a uint8 ``out``) uint8; ``out`` may have
+        spare rows per slot ([F, >= nrows, W, 3]), as in render_frames. ``batch`` frames
+        share one camera upload and one launch (rtx_render_sequence; default: all of them).
+        The culling structures of an upload cover the time range of all its windows, so
+        batches of a long sequence can render faster; the result does not depend on it.
+        ``frames=(first, count)`` renders only those frames of the sequence (into ``count``
+        slots). ``counters`` accumulate over all rendered frames. vc.motion_times is
+        neither read nor changed; a later render() uploads the ordinary camera again."""
+        windows = sequence_windows(windows)
+        first, count = (0, len(windows)) if frames is None else (int(frames[0]), int(frames[1]))
+        if first < 0 or count < 1 or first + count > len(windows):
+            raise ValueError("frames=(first, count) must lie inside the %d windows" % len(windows))
+        batch = len(windows) if batch is None else int(batch)
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
+        H, W = self.vc.height, strip_columns(self.vc.width, 0, 1)[1]
+        if groups is not None:
+            nrows = int(N.load().rtx_group_rows(H, int(groups[0]), int(groups[1])))
+            if nrows < 0:
+                raise ValueError("groups=(k, n) needs 0 <= k < n")
+        if nrows is None:
+            nrows = H - row0
+        if out is None:
+            out = torch.empty((count, nrows, W, 3), dtype=torch.uint8 if rgb8 else torch.float32, device="cuda")
+        if out.dim() != 4 or out.shape[0] != count or out.shape[1] < nrows or tuple(out.shape[2:]) != (W, 3) \
+                or out.dtype not in (torch.float32, torch.uint8) or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 or uint8 CUDA tensor [%d, >= %d, %d, 3]"
+                             % (count, nrows, W))
+        if counters is not None and (counters.numel() < N.RTX_COUNTERS or counters.dtype != torch.int64
+                                     or not counters.is_cuda):
+            raise ValueError("counters must be an int64 CUDA tensor with >= %d entries" % N.RTX_COUNTERS)
+        st = stream if stream is not None else torch.cuda.current_stream()
+        cnt = C.c_void_p(counters.data_ptr() if counters is not None else 0)
+        fn, a, b = ("rtx_render_sequence", row0, nrows) if groups is None else \
+            ("rtx_render_groups_sequence",) + tuple(groups)
+        stride = int(out.stride(0) * out.element_size())
+        for k0 in range(0, count, batch):
+            n = min(batch, count - k0)
+            if batch >= count:  # one upload of the whole sequence: the library picks the frames
+                self._set_camera(0, 1, windows)
+                frame0 = first
+            else:               # each batch uploads its own windows
+                self._set_camera(0, 1, windows[first + k0:first + k0 + n])
+                frame0 = 0
+            N.call(fn, self._native.h, int(a), int(b), C.c_void_p(out.data_ptr() + k0 * stride),
+                   int(out.dtype == torch.uint8), frame0, n, stride, cnt, C.c_void_p(st.cuda_stream))
         return out
 
     def render(self, subimage: int = 0, tasks: int = 1) -> np.ndarray:
