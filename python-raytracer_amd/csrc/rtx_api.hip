@@ -74,7 +74,8 @@ enum Opt {
     OPT_SPLIT, OPT_SPLIT_BYTES, OPT_SPLIT_RATIO, OPT_BINS, OPT_HEAVY_TILES, OPT_LENS_BINS, OPT_LGRID, OPT_DSGRID, OPT_DSGRID_MIN,
     OPT_SELF_SKIP, OPT_TILE_SCHED, OPT_XCD_MAP, OPT_TILE_BLOCK, OPT_PRIM_ORIGIN, OPT_SPP, OPT_SPP_MIN, OPT_JIT, OPT_JIT_BAKE, OPT_JIT_EXT,
     OPT_JIT_DUMP, OPT_JIT_IDLE_BAKED, OPT_JIT_DISK_BAKED, OPT_JIT_CACHE, OPT_JIT_FLAGS, OPT_JIT_ILP, OPT_JIT_ASYNC,
-    OPT_DEV_BINS, OPT_CHUNK_MODE, OPT_BIN_LDS, OPT_JIT_CSG, OPT_CSG_RAYS, OPT_CSG_SHADE, OPT_SETUP_LOG, OPT_COUNT
+    OPT_DEV_BINS, OPT_CHUNK_MODE, OPT_BIN_LDS, OPT_JIT_CSG, OPT_CSG_RAYS, OPT_CSG_SHADE, OPT_SETUP_LOG, OPT_SHADOW_BINS,
+    OPT_COUNT
 };
 struct OptDef {
     const char* name;
@@ -115,6 +116,7 @@ constexpr OptDef kOpts[OPT_COUNT] = {
     {"csg_rays", 3, false},                   // their rays in registers (bit 0: trace, bit 1: shadow), else the LDS stack
     {"csg_shade", 0, false},                  // the shade pass compiled with them (measured no faster)
     {"setup_log", 0, false},                  // print the host time of each rtx_camera_set step
+    {"shadow_bins", 1, false},                // per-bin occluder masks of level-0 shadow rays (2: scenes with secondary rays too)
 };
 struct OptVal {
     double v;
@@ -1187,6 +1189,308 @@ bool primary_bins(const HostScene& H, const rtx_camera_desc* c, const std::vecto
     return true;
 }
 
+// Shadow bins (SceneView::bin_shadow): which spheres and boxes can occlude a light's shadow
+// ray from a camera ray's hit point, per 8x8 bin of a pinhole camera (primary_bins' bins and
+// bit layout) and light. Flat scenes of static planes, spheres and boxes only.
+//
+// The hit points of a bin lie in the pyramid of its corner rays (grown by `margin` x 2
+// pixels, as the bins' rectangles are), on a plane or on an object of the bin's object
+// mask: inside the hull of the points P = the corner rays' hits on each plane (every corner
+// ray must meet the plane at |d.n| >= 1e-3 |n|, or none may: otherwise every bit stays set)
+// and, per object of the mask, the pyramid's slice between the nearest and farthest distance
+// from the origin of the object's (inflated, swept) box. A point light's shadow segments
+// then lie in Z = hull(P + {L}), a directional light's rays in Z = hull(P) + {t D, t >= 0}.
+// Object k, grown by margin x (2^-8 (max |p - c| + r), the bins' rule -- 2^-10 for a box --
+// plus the hit points' own offset rho: a plane hit lies within 2^-19 |n|_1 (|p0|_1 + |o|_1 +
+// |P|_1) of its plane, plane_self_limits, so within that over the smallest corner
+// |d.n| / |n| of the exact ray's hit), cannot occlude when a plane separates it from Z: bit
+// (l, k) is cleared only when a direction u (from Gilbert's closest-point iteration toward
+// the object's centre, fp64) has max_Z u.z < min_k u.x. Moving objects and the 17th and
+// later of a kind are always tested. One bin costs ~2 us of host time, 1080p's 32,400 far
+// more than a camera upload may: rtx_camera_set runs sb_bin on the device (k_shadow_bins,
+// one thread per bin); the host loop (shadow_bins) serves the tests' host emulation.
+// margin 0 (tests): no margin at all -- the table then loses shadow tests that pass
+// (tests/test_shadow_bins.py: spheres within fp32 rounding of a tile's Z).
+struct SbV { double x, y, z; };
+struct SbPlane { SbV n; double num, dperp0; };  // unit normal, the origin's signed distance, the hits' offset bound
+struct SbObj { SbV lo, hi, ctr; double r; uint32_t bit; int32_t sphere, always, pad; };
+struct SbLight { SbV v; int32_t point, pad; };  // position, or the direction toward the light
+constexpr int kSbPlanes = 8, kSbObjs = 32, kSbLights = 8, kSbSeen = 8, kSbPoints = 4 * kSbPlanes + 8 * kSbSeen;
+struct SbScene {
+    SbV o, cu, cv, cw;
+    double d, dx, dy, margin, omag;
+    int32_t W, H, bins_x, bins_y, NL, n_plane, n_obs, pad;
+    uint32_t all_bits, always_bits;
+    SbPlane planes[kSbPlanes];
+    SbObj obs[kSbObjs];
+    SbLight lights[kSbLights];
+};
+RTX_HD SbV sb_sub(SbV a, SbV b) { return SbV{a.x - b.x, a.y - b.y, a.z - b.z}; }
+RTX_HD double sb_dot(SbV a, SbV b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+RTX_HD SbV sb_axpy(SbV a, double t, SbV b) { return SbV{a.x + t * b.x, a.y + t * b.y, a.z + t * b.z}; }
+RTX_HD bool sb_fin(SbV a) { return __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z); }
+
+// max over Z of u.z < min over the grown object of u.x, for some u of Gilbert's iteration
+RTX_HD bool sb_separated(const SbV* P, int n, const SbLight& Lt, const SbObj& q, double grow) {
+    SbV x = P[0];
+    for (int it = 0; it < 12; ++it) {
+        SbV u = sb_sub(q.ctr, x);
+        double uu = sb_dot(u, u);
+        if (!(uu > 0.0)) return false;
+        // x, a point of Z, inside the object: it reaches Z
+        if (q.sphere ? uu <= (q.r + grow) * (q.r + grow)
+                     : (x.x >= q.lo.x && x.x <= q.hi.x && x.y >= q.lo.y && x.y <= q.hi.y && x.z >= q.lo.z && x.z <= q.hi.z))
+            return false;
+        if (!Lt.point) {
+            // Z runs to infinity along D: move to the closest point of x + t D, or tilt u
+            // until u.D < 0 for certain (max over Z is finite only then)
+            const double dd = sb_dot(Lt.v, Lt.v), ud = sb_dot(u, Lt.v), thr = 1e-9 * sqrt(uu * dd);
+            if (ud > thr) {
+                x = sb_axpy(x, ud / dd, Lt.v);
+                continue;
+            }
+            if (ud > -thr) {
+                u = sb_axpy(u, -(ud + thr) / dd, Lt.v);
+                uu = sb_dot(u, u);
+                if (!(uu > 0.0)) return false;
+            }
+        }
+        double m = sb_dot(u, P[0]);
+        int best = 0;
+        for (int i = 1; i < n; ++i) {
+            const double v = sb_dot(u, P[i]);
+            if (v > m) { m = v; best = i; }
+        }
+        SbV s = P[best];
+        if (Lt.point) {
+            const double v = sb_dot(u, Lt.v);
+            if (v > m) { m = v; s = Lt.v; }
+        }
+        double omin;
+        if (q.sphere) {
+            omin = sb_dot(u, q.ctr) - (q.r + grow) * sqrt(uu);
+        } else {
+            omin = fmin(u.x * (q.lo.x - grow), u.x * (q.hi.x + grow)) + fmin(u.y * (q.lo.y - grow), u.y * (q.hi.y + grow)) +
+                   fmin(u.z * (q.lo.z - grow), u.z * (q.hi.z + grow));
+        }
+        if (m < omin - 1e-9 * (fabs(m) + fabs(omin) + 1.0)) return true;
+        const SbV w = sb_sub(s, x);
+        const double ww = sb_dot(w, w), t = ww > 0.0 ? sb_dot(u, w) / ww : 0.0;
+        if (!(t > 1e-12)) return false;  // x is Z's closest point: the object reaches Z
+        x = sb_axpy(x, fmin(t, 1.0), w);
+    }
+    return false;
+}
+
+// Bin (bx, by)'s words: out[light].
+RTX_HD void sb_bin(const SbScene& S, const float* xs, const float* ys, const uint32_t* objmask, int32_t bx, int32_t by,
+                   uint32_t* out) {
+    for (int32_t l = 0; l < S.NL; ++l) out[l] = S.all_bits;
+    // the bin's corner rays
+    const int32_t c0 = 8 * bx, c1 = (8 * bx + 8 < S.W ? 8 * bx + 8 : S.W) - 1;
+    const int32_t r0 = 8 * by, r1 = (8 * by + 8 < S.H ? 8 * by + 8 : S.H) - 1;
+    const double px = 2.0 * S.margin * S.dx, py = 2.0 * S.margin * S.dy;
+    const double xl = (double)xs[c0] - px, xh = (double)xs[c1] + px;
+    const double yl = (double)ys[S.H - 1 - r1] - py, yh = (double)ys[S.H - 1 - r0] + py;
+    if (!(xl < xh && yl < yh)) return;
+    SbV dir[4];
+    for (int q = 0; q < 4; ++q) {
+        const double x = (q & 1) ? xh : xl, y = (q & 2) ? yh : yl;
+        const SbV d{x * S.cu.x + y * S.cv.x - S.d * S.cw.x, x * S.cu.y + y * S.cv.y - S.d * S.cw.y,
+                    x * S.cu.z + y * S.cv.z - S.d * S.cw.z};
+        const double dd = sqrt(sb_dot(d, d));
+        if (!(dd > 0.0) || !__builtin_isfinite(dd)) return;
+        dir[q] = SbV{d.x / dd, d.y / dd, d.z / dd};
+    }
+    SbV P[kSbPoints];
+    int np = 0;
+    double rho = 0.0;
+    for (int32_t k = 0; k < S.n_plane; ++k) {
+        const SbPlane& pl = S.planes[k];
+        const double sg = pl.num > 0.0 ? 1.0 : -1.0;
+        double g[4], gmin = INFINITY, gmax = -INFINITY;
+        for (int q = 0; q < 4; ++q) {
+            g[q] = sg * sb_dot(dir[q], pl.n);
+            gmin = fmin(gmin, g[q]);
+            gmax = fmax(gmax, g[q]);
+        }
+        if (gmax <= 0.0) continue;  // no ray of the bin meets it
+        if (!(gmin >= 1e-3)) return;
+        double mp = 0.0;
+        for (int q = 0; q < 4; ++q) {
+            const SbV p = sb_axpy(S.o, fabs(pl.num) / g[q], dir[q]);
+            P[np++] = p;
+            mp = fmax(mp, fabs(p.x) + fabs(p.y) + fabs(p.z));
+        }
+        rho = fmax(rho, (pl.dperp0 + 0x1p-18 * mp) / gmin + 0x1p-20 * mp);
+    }
+    const uint32_t om = objmask[(int64_t)by * S.bins_x + bx];
+    if (om) {
+        // an object's hit points: the pyramid between the nearest and the farthest distance from o
+        // of its box; the far cap's corners lie at tfar / cos(the pyramid's half angle), beyond
+        // the sphere of radius tfar around o
+        const SbV mid{dir[0].x + dir[1].x + dir[2].x + dir[3].x, dir[0].y + dir[1].y + dir[2].y + dir[3].y,
+                      dir[0].z + dir[1].z + dir[2].z + dir[3].z};
+        const double mm = sqrt(sb_dot(mid, mid));
+        double cosa = 1.0;
+        for (int q = 0; q < 4; ++q) cosa = fmin(cosa, sb_dot(mid, dir[q]) / mm);
+        if (!(cosa > 0.1)) return;
+        int seen = 0;
+        for (int32_t i = 0; i < S.n_obs; ++i) {
+            const SbObj& q = S.obs[i];
+            if (!(om & q.bit)) continue;
+            if (++seen > kSbSeen) return;
+            const double ov[3] = {S.o.x, S.o.y, S.o.z}, lo[3] = {q.lo.x, q.lo.y, q.lo.z}, hi[3] = {q.hi.x, q.hi.y, q.hi.z};
+            double n2 = 0.0, f2 = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                const double dn = fmax(0.0, fmax(lo[a] - ov[a], ov[a] - hi[a]));
+                const double df = fmax(fabs(lo[a] - ov[a]), fabs(hi[a] - ov[a]));
+                n2 += dn * dn;
+                f2 += df * df;
+            }
+            const double pad = 1e-5 * (S.omag + sqrt(f2));
+            const double tn = fmax(0.0, sqrt(n2) - pad), tf = (sqrt(f2) + pad) / cosa;
+            for (int e = 0; e < 4; ++e) {
+                P[np++] = sb_axpy(S.o, tn, dir[e]);
+                P[np++] = sb_axpy(S.o, tf, dir[e]);
+            }
+        }
+    }
+    if (!__builtin_isfinite(rho)) return;
+    for (int i = 0; i < np; ++i)
+        if (!sb_fin(P[i])) return;
+    for (int32_t l = 0; l < S.NL; ++l) {
+        if (np == 0) {  // no hit point at all
+            out[l] = S.always_bits;
+            continue;
+        }
+        uint32_t m = S.all_bits;
+        for (int32_t i = 0; i < S.n_obs; ++i) {
+            const SbObj& q = S.obs[i];
+            if (q.always || (om & q.bit)) continue;  // (its own hit points are in Z)
+            double dmax = 0.0;
+            for (int j = 0; j < np; ++j) dmax = fmax(dmax, sb_dot(sb_sub(P[j], q.ctr), sb_sub(P[j], q.ctr)));
+            const double grow = S.margin * ((q.sphere ? 0x1p-8 : 0x1p-10) * (sqrt(dmax) + q.r) + rho);
+            if (sb_separated(P, np, S.lights[l], q, grow)) m &= ~q.bit;
+        }
+        out[l] = m | S.always_bits;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_shadow_bins(const SbScene* __restrict__ S, const float* __restrict__ xs,
+                                                     const float* __restrict__ ys, const uint32_t* __restrict__ objmask,
+                                                     uint32_t* __restrict__ out) {
+    const int32_t b = (int32_t)(blockIdx.x * 64 + threadIdx.x);
+    if (b >= S->bins_x * S->bins_y) return;
+    sb_bin(*S, xs, ys, objmask, b % S->bins_x, b / S->bins_x, out + (int64_t)b * S->NL);
+}
+
+// The camera's SbScene; false: the camera or the scene gets no shadow bins.
+bool shadow_bins_scene(const HostScene& H, const rtx_camera_desc* c, int32_t bins_x, double margin, SbScene& S) {
+    auto ldd = [](const float* p) { return SbV{(double)p[0], (double)p[1], (double)p[2]}; };
+    auto amax = [](SbV a) { return std::max(std::fabs(a.x), std::max(std::fabs(a.y), std::fabs(a.z))); };
+    std::memset(&S, 0, sizeof(S));
+    const int32_t NL = (int32_t)H.lights.size();
+    if (NL < 1 || NL > kSbLights || H.n_mesh > 0 || H.has_ext || H.n_sphere + H.n_box == 0 || H.n_sphere + H.n_box > kSbObjs ||
+        H.n_plane > kSbPlanes)
+        return false;
+    if (c->ncols < 2 || c->height < 2 || bins_x != (c->ncols + 7) / 8) return false;
+    const bool pinhole = c->n_dof == 1 && c->n_aa == 1 && c->jitter == RTX_JITTER_OFF &&
+                         c->dof_origins[0] == c->position[0] && c->dof_origins[1] == c->position[1] &&
+                         c->dof_origins[2] == c->position[2];
+    if (!pinhole) return false;
+    S.W = c->ncols; S.H = c->height; S.bins_x = bins_x; S.bins_y = (c->height + 7) / 8; S.NL = NL;
+    S.o = ldd(c->aa_origins); S.cu = ldd(c->u); S.cv = ldd(c->v); S.cw = ldd(c->w);
+    S.d = c->d;
+    S.margin = margin;
+    S.omag = amax(S.o);
+    if (!sb_fin(S.o) || !sb_fin(S.cu) || !sb_fin(S.cv) || !sb_fin(S.cw) || !std::isfinite(S.d)) return false;
+    for (int32_t i = 1; i < S.W; ++i) S.dx = std::max(S.dx, (double)c->xs[i] - (double)c->xs[i - 1]);  // the widest pixel steps
+    for (int32_t j = 1; j < S.H; ++j) S.dy = std::max(S.dy, (double)c->ys[j] - (double)c->ys[j - 1]);
+    if (!(S.dx > 0.0) || !(S.dy > 0.0) || !std::isfinite(S.dx + S.dy)) return false;
+    double tlo = INFINITY, thi = -INFINITY;
+    for (float t : camera_times(c)) {
+        tlo = std::min(tlo, (double)t);
+        thi = std::max(thi, (double)t);
+    }
+    S.n_plane = H.n_plane;
+    for (int32_t k = 0; k < H.n_plane; ++k) {
+        const DObj& ob = H.objs[k];
+        if (ob.has_speed) return false;
+        const SbV n = ldd(ob.b), p0 = ldd(ob.a);
+        const double nn = std::sqrt(sb_dot(n, n));
+        if (!sb_fin(n) || !sb_fin(p0) || !(nn > 0.0)) return false;
+        SbPlane& pl = S.planes[k];
+        pl.n = SbV{n.x / nn, n.y / nn, n.z / nn};
+        pl.num = sb_dot(sb_sub(p0, S.o), pl.n);
+        const double n1 = (std::fabs(n.x) + std::fabs(n.y) + std::fabs(n.z)) / nn;
+        // the hit's offset from the plane: dperp0 + 2^-19 n1 |P|_1
+        pl.dperp0 = 0x1p-19 * n1 * (std::fabs(p0.x) + std::fabs(p0.y) + std::fabs(p0.z) + std::fabs(S.o.x) + std::fabs(S.o.y) + std::fabs(S.o.z));
+        if (!(std::fabs(pl.num) > 1e-9 * (1.0 + amax(p0) + S.omag))) return false;
+    }
+    // spheres and boxes: the box that holds their hit points (primary_bins' inflation and
+    // sweep) and, as occluders, their exact shape (sb_bin grows it)
+    S.n_obs = H.n_sphere + H.n_box;
+    for (int32_t k = 0; k < S.n_obs; ++k) {
+        const DObj& ob = H.objs[H.n_plane + k];
+        SbObj& q = S.obs[k];
+        q.sphere = k < H.n_sphere;
+        const int32_t kk = q.sphere ? k : k - H.n_sphere;
+        q.bit = 1u << ((q.sphere ? 0 : 16) + (kk & 15));
+        q.always = ob.has_speed || (q.sphere ? H.n_sphere : H.n_box) > 16;
+        double lo[3], hi[3];
+        if (q.sphere) {
+            q.ctr = ldd(ob.a);
+            q.r = std::fabs(ob.radius);
+            const SbV oc = sb_sub(q.ctr, S.o);
+            const SbV sp = ob.has_speed ? ldd(ob.speed) : SbV{0, 0, 0};
+            const double mt = std::max(std::fabs(tlo), std::fabs(thi));
+            const double re = q.r + 0x1p-8 * (std::sqrt(sb_dot(oc, oc)) + std::sqrt(sb_dot(sp, sp)) * mt + q.r);
+            lo[0] = q.ctr.x - re; lo[1] = q.ctr.y - re; lo[2] = q.ctr.z - re;
+            hi[0] = q.ctr.x + re; hi[1] = q.ctr.y + re; hi[2] = q.ctr.z + re;
+        } else {
+            for (int a = 0; a < 3; ++a) {
+                const double p = 1e-5 * (std::fabs((double)ob.a[a]) + std::fabs((double)ob.b[a]) + S.omag);
+                lo[a] = std::min((double)ob.a[a], (double)ob.b[a]) - p;
+                hi[a] = std::max((double)ob.a[a], (double)ob.b[a]) + p;
+            }
+            q.ctr = SbV{0.5 * (lo[0] + hi[0]), 0.5 * (lo[1] + hi[1]), 0.5 * (lo[2] + hi[2])};
+            q.r = 0.5 * std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
+        }
+        if (ob.has_speed)
+            for (int a = 0; a < 3; ++a) {
+                const double s0 = (double)ob.speed[a] * tlo, s1 = (double)ob.speed[a] * thi;
+                const double pad = 1e-5 * (std::fabs(lo[a]) + std::fabs(hi[a]) + std::fabs(s0) + std::fabs(s1));
+                lo[a] += std::min(s0, s1) - pad;
+                hi[a] += std::max(s0, s1) + pad;
+            }
+        q.lo = SbV{lo[0], lo[1], lo[2]};
+        q.hi = SbV{hi[0], hi[1], hi[2]};
+        if (!sb_fin(q.lo) || !sb_fin(q.hi) || !sb_fin(q.ctr) || !std::isfinite(q.r)) return false;
+        S.all_bits |= q.bit;
+        if (q.always) S.always_bits |= q.bit;
+    }
+    for (int32_t l = 0; l < NL; ++l) {
+        S.lights[l].point = H.lights[l].type == LIGHT_POINT;
+        S.lights[l].v = ldd(S.lights[l].point ? H.lights[l].vec : H.lights[l].negvec);
+        if (!sb_fin(S.lights[l].v) || (!S.lights[l].point && !(sb_dot(S.lights[l].v, S.lights[l].v) > 0.0))) return false;
+    }
+    return true;
+}
+
+// The table on the host (the tests' host emulation): smask[bin * n_lights + light].
+[[maybe_unused]] bool shadow_bins(const HostScene& H, const rtx_camera_desc* c, const std::vector<uint32_t>& objmask,
+                                  int32_t bins_x, std::vector<uint32_t>& smask, double margin = 1.0) {
+    smask.clear();
+    SbScene S;
+    if (!shadow_bins_scene(H, c, bins_x, margin, S) || objmask.size() < (size_t)S.bins_x * S.bins_y) return false;
+    smask.assign((size_t)S.bins_x * S.bins_y * S.NL, S.all_bits);
+    for (int32_t by = 0; by < S.bins_y; ++by)
+        for (int32_t bx = 0; bx < S.bins_x; ++bx)
+            sb_bin(S, c->xs, c->ys, objmask.data(), bx, by, smask.data() + ((size_t)by * S.bins_x + bx) * S.NL);
+    return true;
+}
+
 // Light grids (DLGrid, rtx_trace.h): shadow rays of point lights against the scene's one
 // top-level mesh. A shadow ray from p toward light L is the line through p and L
 // (Mesh.shadow_intersect has no t_max, so the part beyond L counts too): every point of
@@ -1918,6 +2222,8 @@ bool jit_spec(const std::string& arch, const SceneView& v, const KParams& kp, co
         opts.push_back("-DRTX_LB_WAVES(MESH,SEC)=7");
     }
     opts.push_back(std::string("-DRTX_PRIMARY_BINS=") + (kp.S.bins_on ? "1" : "0"));
+    // (only kernels of cameras with shadow bins: the others' option lists stay as they were)
+    if (kp.S.bins_on && kp.S.bin_shadow != nullptr) opts.push_back("-DRTX_SHADOW_BINS=1");
     // a mesh's face bins read through LDS (rtx_trace.h BinLds; option bin_lds)
     if (mesh && !ext && kp.S.bins_on && kp.S.mesh_bins && opt_on(OPT_BIN_LDS)) opts.push_back("-DRTX_BIN_LDS=1");
     opts.push_back(std::string("-DRTX_LIGHT_GRIDS=") + (v.lgrid_on ? "1" : "0"));
@@ -2978,6 +3284,14 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
         o_hitems = st.put(hitems);
         // (o_mhits: below, device-filled)
     }
+    // shadow bins (option shadow_bins 0: none): flat scenes of primary and shadow rays. Scenes
+    // with secondary rays get none, as with the planes' self tests: most of their shadow rays
+    // leave deeper levels, which would pay the check and never skip
+    SbScene sbs;
+    size_t o_sbs = 0, o_bshadow = 0;
+    const bool sbins = bins && opt_on(OPT_SHADOW_BINS) && (!s->has_secondary || opt(OPT_SHADOW_BINS) >= 2) && !s->has_mesh && !s->has_ext &&
+                       shadow_bins_scene(s->h_bins, c, bins_x, 1.0, sbs);
+    if (sbins) o_sbs = st.put(&sbs, sizeof(sbs));  // (o_bshadow: below, device-filled)
     slog.mark("bins", st.size());
     // the measured tile schedule (tile_schedule): identity order until measured
     const bool tsched = tile_sched_enabled() && !s->has_ext && (s->has_secondary || s->has_mesh);
@@ -3001,6 +3315,7 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
         o_bz = st.put(nullptr, sizeof(float) * dev_pairs, true);
     }
     if (heavy) o_mhits = st.put(nullptr, sizeof(uint2) * 64 * hitems.size(), true);
+    if (sbins) o_bshadow = st.put(nullptr, sizeof(uint32_t) * (size_t)sbs.bins_x * sbs.bins_y * sbs.NL, true);
     if (tsched) {
         const int64_t nw = (tiles + kBlock<false> / 64 - 1) / (kBlock<false> / 64) * (kBlock<false> / 64);
         o_ttime = st.put(nullptr, sizeof(uint32_t) * nw, true);
@@ -3042,6 +3357,7 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
         k.S.bins_x = bins_x;
         k.S.bins_on = 1;
     }
+    if (sbins) k.S.bin_shadow = (cptr<uint32_t>)(D + o_bshadow);
     s->heavy_n = 0;
     s->d_heavy_items = nullptr;
     s->d_mesh_hits = nullptr;
@@ -3091,6 +3407,16 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
     for (const auto& r : st.runs())  // (the segments the device fills are not uploaded)
         if ((rc = pinned_upload(s, D + r.first, r.second - r.first, r.first))) return rc;
     slog.mark("upload");
+    if (sbins) {  // the shadow bins, from the tables just uploaded (one thread per bin)
+        const int32_t nbin = sbs.bins_x * sbs.bins_y;
+        hipLaunchKernelGGL(k_shadow_bins, dim3((unsigned)((nbin + 63) / 64)), dim3(64), 0, nullptr,
+                           reinterpret_cast<const SbScene*>(D + o_sbs), reinterpret_cast<const float*>(D + o_xs),
+                           reinterpret_cast<const float*>(D + o_ys), reinterpret_cast<const uint32_t*>(D + o_bmask),
+                           reinterpret_cast<uint32_t*>(D + o_bshadow));
+        RTX_HIP(hipGetLastError());
+        RTX_HIP(hipStreamSynchronize(nullptr));
+        slog.mark("shadow bins (device)");
+    }
     if (dev_faces) {
         if ((rc = mesh_bins_dev2(s, bins_x, (int32_t)(bstart.size() - 1), dev_pairs, reinterpret_cast<int32_t*>(D + o_bfaces),
                                  reinterpret_cast<float*>(D + o_bz))))

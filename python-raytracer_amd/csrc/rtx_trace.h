@@ -370,7 +370,22 @@ struct SceneView {
     // the largest max |p_i| of a camera ray's hit point p on that plane whose own shadow
     // test toward the light cannot pass (-1: none); null: no skips
     cptr<float> plane_self;
+    // Shadow bins (per camera; rtx_api.hip shadow_bins): [bin][light] the spheres (bits
+    // 0-15) and boxes (16-31) that can occlude light's shadow ray from a camera ray's hit
+    // point in that 8x8 bin (bin_objmask's layout and bins); null: every object is tested
+    cptr<uint32_t> bin_shadow;
 };
+
+// Kernels that read SceneView::bin_shadow. Scene-specialized kernels do only when their
+// camera has the table (rtx_api.hip jit_spec defines it then); everything else checks the
+// pointer at run time.
+#ifndef RTX_SHADOW_BINS
+#ifdef RTX_FIXED_COUNTS
+#define RTX_SHADOW_BINS 0
+#else
+#define RTX_SHADOW_BINS 1
+#endif
+#endif
 
 // Mesh records read by the hot BVH walks (closest_hit / occluded). Scene-specialized
 // kernels built with RTX_LDS_TRIS / RTX_LDS_LEAVES (the scene's triangle and BVH-node
@@ -2370,7 +2385,8 @@ RTX_HD Hit closest_hit(const SceneView& S, f3 o, f3 d, float time, Tally& tl, co
 }
 
 // ------------------------------------------------------------------ shadow any-hit
-RTX_HD void origin_terms(const SceneView& S, f3 o, float time, OriginTerms& T) {
+// smask (wave-uniform): the spheres (bit k & 15) whose terms some shadow test will read
+RTX_HD void origin_terms(const SceneView& S, f3 o, float time, OriginTerms& T, uint32_t smask = ~0u) {
 #ifdef RTX_FIXED_COUNTS
     int oi = 0;
     for (int k = 0; k < RTX_NPLANE(S); ++k, ++oi) {
@@ -2378,6 +2394,7 @@ RTX_HD void origin_terms(const SceneView& S, f3 o, float time, OriginTerms& T) {
         T.pnum[k] = dot(sub(moved(ob, ob.a, time), o), ld3(ob.b));
     }
     for (int k = 0; k < RTX_NSPHERE(S); ++k, ++oi) {
+        if (RTX_SHADOW_BINS && !((smask >> (k & 15)) & 1u)) continue;
         const DObj ob = S.objs[oi];
         T.soc[k] = sub(o, moved(ob, ob.a, time));
         T.sq[k] = dot(T.soc[k], T.soc[k]);
@@ -2470,7 +2487,7 @@ RTX_HD DSCell dir_shadow_mask(const SceneView& S, int light, f3 p) {
 // light grid, if any, may stand in for the mesh's BVH walk).
 template <bool MESH, bool X, bool COUNT>
 RTX_HD bool occluded(const SceneView& S, f3 o, f3 d, double t_max, float time, Tally& tl, const HStack& hs,
-                     const OriginTerms* ot = nullptr, int light = -1, int32_t self_obj = -1) {
+                     const OriginTerms* ot = nullptr, int light = -1, int32_t self_obj = -1, uint32_t bmask = ~0u) {
     const float tmax32 = (float)t_max;
     // the floats around t_max (both tmax32 for the shader's 1.0 and inf)
     const float tmax_dn = (double)tmax32 > t_max ? nextafterf(tmax32, -INFINITY) : tmax32;
@@ -2538,6 +2555,8 @@ RTX_HD bool occluded(const SceneView& S, f3 o, f3 d, double t_max, float time, T
     const uint32_t smask = sc.obj;
     for (int k = 0; k < RTX_NSPHERE(S); ++k, ++oi) {  // simple_geometry.py:48-72 (shadow_epsilon 1e-3)
         if (RTX_PROBE(19)) continue;  // cost probe: spheres never occlude
+        // (wave-uniform) the camera's shadow bins: it cannot occlude from this tile's hit points
+        if (RTX_SHADOW_BINS && !((bmask >> (k & 15)) & 1u)) continue;
         const bool sl = ((smask >> (k & 15)) & 1u) != 0u;
         if (!RTX_ANY(sl && !occ)) continue;
         const DObj ob = S.objs[oi];
@@ -2576,12 +2595,13 @@ RTX_HD bool occluded(const SceneView& S, f3 o, f3 d, double t_max, float time, T
     // the reciprocals once some lane's ray may meet a box (meshes: once a lane passes a
     // bounding volume)
     bool have_ri = false;
-    if (RTX_NBOX(S) > 0 && RTX_ANY(!occ && (smask >> 16) != 0u)) {
+    if (RTX_NBOX(S) > 0 && (!RTX_SHADOW_BINS || (bmask >> 16) != 0u) && RTX_ANY(!occ && (smask >> 16) != 0u)) {
         ri = ray_inv(o, d);
         have_ri = true;
     }
     for (int k = 0; k < RTX_NBOX(S); ++k, ++oi) {  // simple_geometry.py:251-294
         if (RTX_PROBE(20)) continue;  // cost probe: boxes never occlude
+        if (RTX_SHADOW_BINS && !((bmask >> (16 + (k & 15))) & 1u)) continue;  // (shadow bins, as above)
         const bool sl = ((smask >> (16 + (k & 15))) & 1u) != 0u && !(oi == self_obj && k < 16 && ((self_boxes >> (16 + k)) & 1u));
         if (!RTX_ANY(sl && !occ)) continue;
         const DObj ob = S.objs[oi];
@@ -2703,8 +2723,18 @@ RTX_HD bool occluded(const SceneView& S, f3 o, f3 d, double t_max, float time, T
                              RTX_FIXED_NL <= 8 && RTX_PLANE_SHADOW_RCP && !RTX_SHADOW_F32)
 #endif
 #if defined(RTX_LIGHTS_TOGETHER) && RTX_LIGHTS_TOGETHER
-RTX_HD uint32_t occluded_points(const SceneView& S, f3 o, const f3* sd, const OriginTerms& ot, int32_t self_obj) {
+// sm: null, or per light the spheres (bit k & 15) that can occlude from this tile
+// (SceneView::bin_shadow, wave-uniform): the others' tests are skipped by scalar branches.
+RTX_HD uint32_t occluded_points(const SceneView& S, f3 o, const f3* sd, const OriginTerms& ot, int32_t self_obj,
+                                cptr<uint32_t> sm = nullptr) {
     constexpr int NL = RTX_FIXED_NL;
+    uint32_t bm[NL];
+    uint32_t bm_any = 0u;
+#pragma unroll
+    for (int li = 0; li < NL; ++li) {
+        bm[li] = (RTX_SHADOW_BINS && sm != nullptr) ? sm[li] : ~0u;
+        bm_any |= bm[li];
+    }
     const double t_max = 1.0;
     const float tmax32 = 1.0f, tmax_up = 1.0f, tmax_lim = nextafterf(1.0f, -INFINITY);
     bool occ[NL];
@@ -2756,12 +2786,15 @@ RTX_HD uint32_t occluded_points(const SceneView& S, f3 o, const f3* sd, const Or
         for (int li = 0; li < NL; ++li) occ[li] = occ[li] || (!skip[li] && hit[li]);
     }
     for (int k = 0; k < RTX_NSPHERE(S); ++k, ++oi) {  // simple_geometry.py:48-72 (shadow_epsilon 1e-3)
+        if (RTX_SHADOW_BINS && !((bm_any >> (k & 15)) & 1u)) continue;  // no light's ray can meet it
         bool need[NL];
         bool any_need = false;
         const DObj ob = S.objs[oi];
 #pragma unroll
         for (int li = 0; li < NL; ++li) {
-            need[li] = !occ[li] && sphere_disc_sign_oc(sd[li], ot.soc[k], ot.sq[k], ob.r2f) >= 0;
+            need[li] = false;
+            if (!RTX_SHADOW_BINS || ((bm[li] >> (k & 15)) & 1u))
+                need[li] = !occ[li] && sphere_disc_sign_oc(sd[li], ot.soc[k], ot.sq[k], ob.r2f) >= 0;
             any_need = any_need || need[li];
         }
         if (!RTX_ANY(any_need)) continue;
@@ -2906,11 +2939,21 @@ RTX_HD double spec_pow(double x, const DMat& m, int pow_bits) {
 // shadow ray is occluded, as a separate pass found it; no shadow ray is traced here.
 template <bool MESH, bool X, bool COUNT>
 RTX_HD f3 regular_lighting(const SceneView& S, f3 dir, f3 pos, f3 normal, const DMat& m, f3 diffuse, float time,
-                           Tally& tl, const HStack& hs, int64_t occ_mask = -1, int32_t self_obj = -1) {
+                           Tally& tl, const HStack& hs, int64_t occ_mask = -1, int32_t self_obj = -1, int32_t sbin = -1) {
     f3 colour = mk(0.0f, 0.0f, 0.0f);
     tally_inc<COUNT>(tl, &Tally::shade);
+    // the tile's shadow bins (sbin: the bin of a camera ray's hit, else -1)
+    cptr<uint32_t> sbm = nullptr;
+    uint32_t sb_any = ~0u;
+#if RTX_SHADOW_BINS
+    if (sbin >= 0 && S.bin_shadow != nullptr) {  // (wave-uniform)
+        sbm = S.bin_shadow + (int64_t)wave_uniform(sbin) * RTX_NLIGHTS(S);
+        sb_any = 0u;
+        for (int li = 0; li < RTX_NLIGHTS(S); ++li) sb_any |= sbm[li];
+    }
+#endif
     OriginTerms ot;
-    origin_terms(S, pos, time, ot);
+    origin_terms(S, pos, time, ot, sb_any);
 #ifdef RTX_FIXED_COUNTS
     const OriginTerms* otp = RTX_NLIGHTS(S) > 1 ? &ot : nullptr;
 #else
@@ -2921,7 +2964,7 @@ RTX_HD f3 regular_lighting(const SceneView& S, f3 dir, f3 pos, f3 normal, const 
         f3 sd[RTX_FIXED_NL];
 #pragma unroll
         for (int li = 0; li < RTX_FIXED_NL; ++li) sd[li] = sub(ld3(S.lights[li].vec), pos);
-        occ_mask = (int64_t)occluded_points(S, pos, sd, ot, self_obj);
+        occ_mask = (int64_t)occluded_points(S, pos, sd, ot, self_obj, sbm);
     }
 #endif
     for (int li = 0; li < RTX_NLIGHTS(S); ++li) {
@@ -2943,7 +2986,8 @@ RTX_HD f3 regular_lighting(const SceneView& S, f3 dir, f3 pos, f3 normal, const 
         tally_inc<COUNT>(tl, &Tally::shadow);
         if (occ_mask >= 0) {
             if ((occ_mask >> li) & 1) continue;
-        } else if (!RTX_PROBE(1) && occluded<MESH, X, COUNT>(S, pos, sdir, t_max, time, tl, hs, otp, li, self_obj)) {
+        } else if (!RTX_PROBE(1) &&
+                   occluded<MESH, X, COUNT>(S, pos, sdir, t_max, time, tl, hs, otp, li, self_obj, sbm ? sbm[li] : ~0u)) {
             continue;
         }
         if (RTX_PROBE(3)) { colour = add(colour, mul(ld3(L.cp), diffuse)); continue; }
@@ -3051,7 +3095,7 @@ RTX_HD f3 cast_ray(const SceneView& S, f3 o, f3 d, float time, Tally& tl, const 
         const f3 diffuse = (X && sf.gobj >= 0) ? get_diffuse(S, S.objs[sf.gobj], sf.position, time) : ld3(m.diffuse);
         // a camera ray's hit (level 0) tells occluded which flat object it lies on
         const f3 L = regular_lighting<MESH, X, COUNT>(S, d, sf.position, n, m, diffuse, time, tl, hs, -1,
-                                                      level == 0 ? h.obj : -1);
+                                                      level == 0 ? h.obj : -1, level == 0 ? bin : -1);
         if (!SEC || !chain) {
             tail = clamp01(L);
             break;
