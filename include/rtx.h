@@ -246,6 +246,28 @@ int rtx_render_groups_sequence(rtx_scene* scene, int32_t phase, int32_t stride, 
                                int32_t frame0, int32_t nframes, int64_t frame_stride_bytes, uint64_t* counters_dev,
                                void* hip_stream);
 
+/* First-hit feature buffers of rows [row0, row0 + nrows) of the strip (no reference
+ * counterpart): what the FIRST sample of each pixel sees -- the ray of DOF origin 0 and AA
+ * origin 0 (provided/scene.py:57-61) with that sample's jitter draw (:63-65, the draw
+ * rtx_render uses for it), at the first motion time of window `frame` (0 for a camera
+ * without a sequence). Buffers are pixel-major with row 0 at the top, like the framebuffer;
+ * each may be NULL (not written), but not all six:
+ *   depth    f32 [nrows][ncols]     fp32 rounding of first_intersect.time (scene.py:86-94), +inf on a miss
+ *   normal   f32 [nrows][ncols][3]  first_intersect.normal as the reference has it (not renormalised), 0
+ *   position f32 [nrows][ncols][3]  first_intersect.position, 0
+ *   albedo   f32 [nrows][ncols][3]  the `diffuse` of _compute_regular_lighting (scene.py:143-146): get_diffuse
+ *                                   of planes and boxes (checkers, textures; also inside hierarchies), else the
+ *                                   material's diffuse, whatever the material's type; 0
+ *   object   i32 [nrows][ncols]     index of the hit's top-level object (as rtx_intersect), -1
+ *   material i32 [nrows][ncols]     index of first_intersect.mat (as rtx_intersect), -1
+ * Every value is bit-identical to the reference's for that ray. Asynchronous on the stream.
+ * RTX_ERR_STATE before rtx_camera_set; RTX_ERR_INVALID for a null scene, a row range outside
+ * the image, six null pointers or a frame outside the camera's sequence; the arguments are
+ * checked before any HIP call. rtx_last_kernel is left as it is. */
+int rtx_render_aov(rtx_scene* scene, int32_t row0, int32_t nrows, int32_t frame, float* depth_dev, float* normal_dev,
+                   float* position_dev, float* albedo_dev, int32_t* object_dev, int32_t* material_dev,
+                   void* hip_stream);
+
 /* Rows rtx_render_groups writes for an image of `height` rows (-1: bad arguments). */
 int32_t rtx_group_rows(int32_t height, int32_t phase, int32_t stride);
 

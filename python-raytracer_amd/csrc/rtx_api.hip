@@ -6,6 +6,8 @@
 //                 sum is accumulated exactly as the reference does; each sample runs the
 //                 iterative cast_ray of rtx_trace.h. Scene records are read with
 //                 wave-uniform indices (scalar loads through the constant cache).
+//   k_aov         one work-item per output pixel: the first sample's closest hit as feature
+//                 buffers (depth, normal, position, albedo, object and material ids)
 //   k_intersect   closest hit of SoA rays (Geometry.intersect + min, scene.py:86-94)
 //   k_occluded    shadow any-hit of SoA rays (Geometry.shadow_intersect, scene.py:160-164)
 //   k_to_rgb8     (v * 255.0) truncated to uint8 (main.py:33)
@@ -3998,6 +4000,43 @@ int rtx_intersect(rtx_scene* s, int64_t n, const float* ro, const float* rd, dou
     if (s->has_mesh) { if (s->has_ext) RTX_ISECT(true, true); else RTX_ISECT(true, false); }
     else { if (s->has_ext) RTX_ISECT(false, true); else RTX_ISECT(false, false); }
 #undef RTX_ISECT
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_render_aov(rtx_scene* s, int32_t row0, int32_t nrows, int32_t frame, float* depth_dev, float* normal_dev,
+                   float* position_dev, float* albedo_dev, int32_t* object_dev, int32_t* material_dev, void* stream) {
+    if (!s) return fail(RTX_ERR_INVALID, "rtx_render_aov: null scene");
+    if (!s->cam_set) return fail(RTX_ERR_STATE, "rtx_render_aov: rtx_camera_set was not called");
+    if (row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > s->kp.height)
+        return fail(RTX_ERR_INVALID, "rtx_render_aov: row range outside the image");
+    if (!depth_dev && !normal_dev && !position_dev && !albedo_dev && !object_dev && !material_dev)
+        return fail(RTX_ERR_INVALID, "rtx_render_aov: no buffer requested (all six pointers are null)");
+    // an ordinary camera holds one window (n_frames 0): frame 0
+    if (frame < 0 || frame >= std::max(s->kp.n_frames, 1))
+        return fail(RTX_ERR_INVALID, "rtx_render_aov: frame " + std::to_string(frame) + " outside the camera's " +
+                                         std::to_string(std::max(s->kp.n_frames, 1)) + " window(s)");
+    if (nrows == 0) return RTX_OK;
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != s->device)
+        return fail(RTX_ERR_STATE, "rtx_render_aov: the scene lives on device " + std::to_string(s->device) +
+                                       ", the current device is " + std::to_string(cur));
+    const int blk = s->has_ext ? kBlock<true> : kBlock<false>;
+    const int64_t nblocks = (launch_items(nrows, s->kp.ncols) + blk - 1) / blk;
+    if (nblocks > 0x7fffffff) return fail(RTX_ERR_INVALID, "rtx_render_aov: launch too large");
+    const AovLaunch L{depth_dev, normal_dev, position_dev, albedo_dev, object_dev, material_dev,
+                      row0,      nrows,      frame * s->kp.n_times, 0};
+    const size_t lds = s->has_ext ? (size_t)s->hlevels * 9 * sizeof(float) * kBlock<true> : 0;
+    const KParams* kp = s->d_kp;
+    const bool jit = s->kp.jitter != RTX_JITTER_OFF;
+#define RTX_AOV(M, X, J) \
+    hipLaunchKernelGGL((k_aov<M, X, J>), dim3((unsigned)nblocks), dim3(kBlock<X>), lds, (hipStream_t)stream, kp, L)
+#define RTX_AOV_J(M, X) \
+    do { if (jit) RTX_AOV(M, X, true); else RTX_AOV(M, X, false); } while (0)
+    if (s->has_mesh) { if (s->has_ext) RTX_AOV_J(true, true); else RTX_AOV_J(true, false); }
+    else { if (s->has_ext) RTX_AOV_J(false, true); else RTX_AOV_J(false, false); }
+#undef RTX_AOV_J
+#undef RTX_AOV
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

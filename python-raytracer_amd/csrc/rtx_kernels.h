@@ -826,6 +826,72 @@ __global__ __launch_bounds__(256) void k_occluded(SceneView S, int64_t n, const 
     occ[i] = occluded<MESH, X, false>(S, o, d, tmax[i], time, tl, hs) ? 1 : 0;
 }
 
+// The per-call block of the first-hit pass (rtx_render_aov): rows [row0, row0 + nrows) of
+// the strip, the frame's first motion time P.times[tbase], and one pointer per buffer
+// (pixel-major like the framebuffer, [nrows][ncols] or [nrows][ncols][3]; null: not wanted).
+struct AovLaunch {
+    float* depth;
+    float* normal;
+    float* position;
+    float* albedo;
+    int32_t* object;
+    int32_t* material;
+    int32_t row0, nrows, tbase, pad;
+};
+
+RTX_HD void put3(float* out, int64_t p, f3 v) {
+    out[3 * p] = v.x;
+    out[3 * p + 1] = v.y;
+    out[3 * p + 2] = v.z;
+}
+
+// What the first sample of each pixel sees (no reference counterpart: the attributes of
+// scene.py:86-94's first_intersect for the ray of DOF origin 0, AA origin 0, scene.py:57-65,
+// with that sample's jitter draw, at the frame's first motion time). render_body's mapping:
+// one lane per pixel, an 8x8 tile per wave, ragged edge lanes inactive, the tile's primary
+// bin under render_body's condition. closest_hit gets no pixel-in-tile (blane -1): a heavy
+// mesh tile walks its face list, since only a render fills SceneView::mesh_hits. A tile
+// row's 8 pixels are one contiguous segment of every buffer (32 B, or 96 B for a vector).
+template <bool MESH, bool X, bool JIT>
+__global__ __launch_bounds__(kBlock<X>) void k_aov(const KParams* __restrict__ Pp, const AovLaunch L) {
+    constexpr int B = kBlock<X>;
+    extern __shared__ float hstack[];  // X: [level][9][thread] (dynamic size)
+    const HStack hs{hstack + threadIdx.x, B};
+    const KParams& P = *Pp;
+    const int32_t ncols = P.ncols;
+    const PixelRC px = pixel_rc(ncols, 0);
+    if (!(px.r < L.nrows && px.c < ncols)) return;
+    const int32_t bin = RTX_TILE == 1 ? primary_bin(P.S, L.row0 + (px.r & ~7), px.c & ~7) : -1;
+    const int j = P.height - 1 - (L.row0 + px.r);  // reference row index (y grows upward)
+    const f3 o = sample_origin<JIT>(P, px.c, j, 0, 0);
+    const f3 d = normalize(sub(pixel_focal(P, px.c, j), ld3(P.dof_o)));  // scene.py:58
+    const float time = P.times[L.tbase];
+    Tally tl = {};
+    HHit hh;
+    const Hit h = closest_hit<MESH, X, false>(P.S, o, d, time, tl, hs, hh, bin, nullptr, -1);
+    const bool hit = h.obj != -1;
+    const bool hier = X && h.obj == kHierHit;
+    Surface sf;
+    sf.position = mk(0.0f, 0.0f, 0.0f);
+    sf.normal = mk(0.0f, 0.0f, 0.0f);
+    sf.mat = -1;
+    sf.gobj = -1;
+    if (hit) sf = resolve_hit<MESH, X>(P.S, h, hh, o, d, time);
+    const int64_t p = (int64_t)px.r * ncols + px.c;
+    if (L.depth) L.depth[p] = !hit ? INFINITY : hier ? (float)hh.t64 : h.t32;
+    if (L.position) put3(L.position, p, sf.position);
+    if (L.normal) put3(L.normal, p, sf.normal);
+    if (L.object) L.object[p] = !hit ? -1 : hier ? h.sub : P.S.objs[h.obj].oid;
+    if (L.material) L.material[p] = sf.mat;
+    if (L.albedo) {  // scene.py:143-146: Plane/AABB hits shade with get_diffuse(position)
+        f3 a = mk(0.0f, 0.0f, 0.0f);
+        if (hit)
+            a = (X && sf.gobj >= 0) ? get_diffuse(P.S, P.S.objs[sf.gobj], sf.position, time)
+                                    : ld3(RTX_MAT(P.S, sf.mat).diffuse);
+        put3(L.albedo, p, a);
+    }
+}
+
 #if !defined(RTX_EXT_TU)  // defined once, in rtx_api.hip
 // The heavy tiles' chunks (one wave per chunk, launched as one-wave blocks), before the
 // render kernel: items (bin, chunk). A launch of rows (row0, nrows) or 8-row groups

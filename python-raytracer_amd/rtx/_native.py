@@ -91,7 +91,8 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_scene_create", "rtx_scene_d
            "rtx_render", "rtx_render_groups", "rtx_group_rows", "rtx_intersect", "rtx_occluded", "rtx_fb_to_rgb8",
            "rtx_render_rgb8", "rtx_render_groups_rgb8", "rtx_last_kernel", "rtx_render_frames",
            "rtx_render_groups_frames", "rtx_jit_modules", "rtx_set_option", "rtx_get_option", "rtx_option_name",
-           "rtx_graph_launch", "rtx_jit_wait", "rtx_render_sequence", "rtx_render_groups_sequence"]
+           "rtx_graph_launch", "rtx_jit_wait", "rtx_render_sequence", "rtx_render_groups_sequence",
+           "rtx_render_aov"]
 
 
 def load():
@@ -120,6 +121,8 @@ def load():
         if hasattr(lib, "rtx_render_sequence"):
             for f in (lib.rtx_render_sequence, lib.rtx_render_groups_sequence):
                 f.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, vp]
+        if hasattr(lib, "rtx_render_aov"):
+            lib.rtx_render_aov.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
         lib.rtx_group_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.rtx_group_rows.restype = C.c_int32
         lib.rtx_intersect.argtypes = [vp, C.c_int64, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]

@@ -16,12 +16,19 @@ steps over [T0, T1) -- default 0 .. the scene's last motion time -- each blurred
 time units with M samples (default: one time per frame), rendered by
 Scene.render_sequence in batches and written as out_0000.png, out_0001.png, ... (or through
 a %d pattern in the name, e.g. frame%03d.png).
+
+    python -m rtx.main --infile S.json --outfile out.png --aovs out.npz [--aov-names depth normal ...]
+
+Besides the image, the first-hit feature buffers of Scene.render_aovs (no reference
+counterpart; default: all six) as (H, W) or (H, W, 3) arrays of one .npz file.
 """
 import argparse
 import json
 import os
 
 import numpy
+
+from .scene import AOV_NAMES
 
 
 def parse(argv=None):
@@ -39,7 +46,21 @@ def parse(argv=None):
                    help="motion times the sequence spans (default: 0 .. the scene's last motion time)")
     p.add_argument("--shutter", type=float, default=0.0, help="time each frame is blurred over")
     p.add_argument("--shutter-samples", type=int, default=1, help="motion times per frame")
+    p.add_argument("--aovs", type=str, default=None, metavar="FILE.npz",
+                   help="also write the first-hit feature buffers (Scene.render_aovs) to this .npz file")
+    p.add_argument("--aov-names", type=str, nargs="+", default=None, metavar="NAME",
+                   help="the buffers to write (default: depth normal position albedo object material)")
     args = p.parse_args(argv)
+    if args.aovs is not None:
+        if args.distributed:
+            p.error("--aovs renders on one GPU: it cannot be combined with --distributed")
+        if args.frames is not None:
+            p.error("--aovs writes the buffers of one frame: it cannot be combined with --frames")
+        if args.aov_names is not None and (len(set(args.aov_names)) != len(args.aov_names)
+                                           or not set(args.aov_names) <= set(AOV_NAMES)):
+            p.error("--aov-names takes distinct names out of: " + " ".join(AOV_NAMES))
+    elif args.aov_names is not None:
+        p.error("--aov-names needs --aovs")
     if args.frames is not None:
         if args.distributed or args.subimage is not None or args.tasks is not None:
             p.error("--frames renders whole frames on one GPU: it cannot be combined with --distributed or "
@@ -89,6 +110,19 @@ def render_frames_to_files(sc, args):
     return names
 
 
+def write_aovs(sc, args):
+    """The chosen feature buffers of the frame (or strip) as one .npz file: name -> (H, W) or
+    (H, W, 3) array, row 0 at the top."""
+    names = tuple(args.aov_names) if args.aov_names is not None else AOV_NAMES
+    kw = {}
+    if args.subimage is not None and args.tasks is not None:
+        kw = dict(subimage=args.subimage, tasks=args.tasks)
+    buffers = sc.render_aovs(names, **kw)
+    with open(args.aovs, "wb") as f:  # (numpy.savez would append ".npz" to a bare name)
+        numpy.savez(f, **{n: buffers[n].cpu().numpy() for n in names})
+    return args.aovs
+
+
 def _scene(args):
     from .scene_parser import load_scene
     if args.resolution is None and args.spp is None:
@@ -132,6 +166,8 @@ def main(argv=None):
     else:
         rgb = full_scene.render_rgb8()  # == (rot90(render()) * 255).astype(uint8), on the device
         Image.fromarray(rgb).save(args.outfile)
+    if args.aovs is not None:
+        write_aovs(full_scene, args)
 
 
 if __name__ == "__main__":

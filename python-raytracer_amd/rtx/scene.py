@@ -23,6 +23,10 @@ from . import track
 from .helperclasses import sunflower, sunflower_many
 
 DEFAULT_SEED = 0x5EED
+# the first-hit feature buffers of Scene.render_aovs (rtx_render_aov)
+AOV_NAMES = ("depth", "normal", "position", "albedo", "object", "material")
+_AOV_VEC = ("normal", "position", "albedo")
+_AOV_INT = ("object", "material")
 
 
 def _ptr(a, ctype):
@@ -447,6 +451,82 @@ class Scene:
             N.call(fn, self._native.h, int(a), int(b), C.c_void_p(out.data_ptr() + k0 * stride),
                    int(out.dtype == torch.uint8), frame0, n, stride, cnt, C.c_void_p(st.cuda_stream))
         return out
+
+    # ------------------------------------------------------------------ first-hit buffers
+    def render_aovs(self, aovs=AOV_NAMES, subimage=0, tasks=1, row0=0, nrows=None, windows=None, frame=0, out=None,
+                    stream=None):
+        """What the first sample of each pixel sees (rtx_render_aov): a dict name -> CUDA
+        tensor for the chosen ``aovs`` of image rows [row0, row0 + nrows) (row 0 = top) of
+        the strip -- "depth" float32 [nrows, W] (+inf on a miss), "normal", "position" and
+        "albedo" float32 [nrows, W, 3] (0), "object" and "material" int32 [nrows, W], the
+        indices in ``objects`` / ``materials`` (-1). The ray is the one of DOF origin 0 and
+        AA origin 0 with that sample's jitter draw, at the first motion time: for a
+        one-sample camera the ray whose colour render() stores. ``windows`` (as
+        render_sequence takes them) makes it the first time of window ``frame`` instead.
+        ``out``: a dict of preallocated contiguous CUDA tensors for some or all of the
+        names. Asynchronous on ``stream`` (default: torch's current stream)."""
+        names = [aovs] if isinstance(aovs, str) else list(aovs)
+        if not names:
+            raise ValueError("render_aovs needs at least one of %s" % (AOV_NAMES,))
+        for n in names:
+            if n not in AOV_NAMES:
+                raise ValueError("unknown feature buffer %r (known: %s)" % (n, ", ".join(AOV_NAMES)))
+        if len(set(names)) != len(names):
+            raise ValueError("a feature buffer is named twice: %s" % (names,))
+        if windows is not None:
+            windows = sequence_windows(windows)
+        frame = int(frame)
+        if not 0 <= frame < (1 if windows is None else len(windows)):
+            raise ValueError("frame %d outside the %d window(s)" % (frame, 1 if windows is None else len(windows)))
+        H, W = self.vc.height, strip_columns(self.vc.width, subimage, tasks)[1]
+        row0 = int(row0)
+        nrows = H - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > H:
+            raise ValueError("rows [%d, %d) outside the image of %d rows" % (row0, row0 + nrows, H))
+        out = {} if out is None else dict(out)
+        for n in out:
+            if n not in names:
+                raise ValueError("out holds %r, which is not among the requested buffers %s" % (n, names))
+        for n in names:
+            shape = (nrows, W, 3) if n in _AOV_VEC else (nrows, W)
+            dtype = torch.int32 if n in _AOV_INT else torch.float32
+            t = out.get(n)
+            if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype
+                                  or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("out[%r] must be a contiguous %s CUDA tensor of shape %s"
+                                 % (n, str(dtype).replace("torch.", ""), shape))
+        self._set_camera(subimage, tasks, windows)
+        for n in names:
+            if out.get(n) is None:
+                out[n] = torch.empty((nrows, W, 3) if n in _AOV_VEC else (nrows, W),
+                                     dtype=torch.int32 if n in _AOV_INT else torch.float32, device="cuda")
+        st = stream if stream is not None else torch.cuda.current_stream()
+        ptr = [C.c_void_p(out[n].data_ptr() if n in out else 0)
+               for n in ("depth", "normal", "position", "albedo", "object", "material")]
+        if nrows > 0:  # (the tensors of an empty block have no storage to point at)
+            N.call("rtx_render_aov", self._native.h, row0, nrows, frame, *ptr, C.c_void_p(st.cuda_stream))
+        return {n: out[n] for n in names}
+
+    def pick(self, col, row, **camera_kwargs):
+        """What pixel (column ``col``, row ``row`` from the top) of the strip shows, as host
+        values: a dict with "object" (the entry of ``objects``, None on a miss), "material"
+        (the entry of ``materials``, or None), "depth" (float, inf), "position", "normal"
+        and "albedo" (numpy float32 [3]). ``camera_kwargs``: render_aovs's subimage, tasks,
+        windows, frame and stream. Renders the one image row holding the pixel."""
+        for k in camera_kwargs:
+            if k not in ("subimage", "tasks", "windows", "frame", "stream"):
+                raise ValueError("pick takes subimage, tasks, windows, frame and stream, not %r" % k)
+        col, row = int(col), int(row)
+        W = strip_columns(self.vc.width, camera_kwargs.get("subimage", 0), camera_kwargs.get("tasks", 1))[1]
+        if not (0 <= col < W and 0 <= row < self.vc.height):
+            raise ValueError("pixel (%d, %d) outside the %d x %d strip" % (col, row, W, self.vc.height))
+        b = self.render_aovs(row0=row, nrows=1, **camera_kwargs)
+        if camera_kwargs.get("stream") is not None:
+            camera_kwargs["stream"].synchronize()
+        b = {n: t[0, col].cpu().numpy() for n, t in b.items()}
+        oi, mi = int(b["object"]), int(b["material"])
+        return dict(object=self.objects[oi] if oi >= 0 else None, material=self.materials[mi] if mi >= 0 else None,
+                    depth=float(b["depth"]), position=b["position"], normal=b["normal"], albedo=b["albedo"])
 
     def render(self, subimage: int = 0, tasks: int = 1) -> np.ndarray:
         """scene.py:35-79 — returns float64 (strip_width, height, 3), [column, row-from-bottom]."""
