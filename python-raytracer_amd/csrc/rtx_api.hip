@@ -2204,6 +2204,9 @@ bool jit_spec(const std::string& arch, const SceneView& v, const KParams& kp, co
     if (!spp) opts.push_back("-DRTX_FIXED_NCOLS=" + std::to_string(kp.ncols));
     if (!spp && !ext && kp.tile_time != nullptr) opts.push_back("-DRTX_TILE_SCHED=1");
     if (!spp && !ext && kp.po_valid) opts.push_back("-DRTX_PRIM_ORIGIN=1");
+    // the XCD-aware block order needs the grid size, a scalar round trip off the implicit
+    // arguments at every wave's start: compiled in only while the option is set (JitSlot::xcd)
+    if (!spp && opt_on(OPT_XCD_MAP)) opts.push_back("-DRTX_XCD_MAP=1");
     if (out8) opts.push_back("-DRTX_OUT8=1");  // uint8 framebuffer (rtx_render_rgb8)
     // secondary-ray frames keep their material index in a register: 3 LDS words per frame
     if (sec && v.n_mats <= 64) opts.push_back("-DRTX_FRAME_MATBITS=6");
@@ -2529,6 +2532,7 @@ struct JitSlot {
     std::string dkey;                     // the device key it loads under (pending)
     bool baked = false;
     bool lds = true;  // a split pass: its rays on the LDS stack (else registers, no LDS)
+    bool xcd = false;  // a render kernel compiled with the XCD map (option xcd_map when resolved)
 };
 
 namespace {
@@ -3403,6 +3407,10 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
         s->d_tile_time = D + o_ttime;
         s->tile_sched = 1;
     }
+    // the camera block's copies of the first DOF and AA origins (rtx_kernels.h KParams),
+    // refreshed with the tables on every upload
+    set3(k.dof0, c->dof_origins);
+    set3(k.aa0, c->aa_origins);
     if ((rc = pinned_reserve(s, host_bytes))) return rc;
     st.write(s->h_cam);
     memcpy(s->h_cam + o_kp, &k, sizeof(KParams));
@@ -3580,7 +3588,7 @@ bool split_enabled() { return opt_on(OPT_SPLIT); }
 // order (MirrorRefraction 41.4 -> 38.6 us, TorusMesh 52.8 -> 49.7 us with orders measured
 // on the same box, profiles/r04/tile_order/; TwoSpheresPlane and DepthOfField gain
 // nothing). The order changes when tiles run, not what they compute.
-int tile_schedule(rtx_scene* s, hipStream_t st, uint32_t wpb) {
+int tile_schedule(rtx_scene* s, hipStream_t st, uint32_t wpb, bool xcd_kernel) {
     if (s->tile_sched != 2) return RTX_OK;
     if (stream_capturing(st)) return RTX_OK;
     const int32_t n = s->kp.tile_n;
@@ -3599,7 +3607,8 @@ int tile_schedule(rtx_scene* s, hipStream_t st, uint32_t wpb) {
     std::vector<int32_t> order((size_t)n);
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return t[a] > t[b]; });
-    s->tile_xcd = opt_on(OPT_XCD_MAP);  // (the frames that follow this table keep its layout)
+    // (the frames that follow this table keep its layout; xcd_kernel: the kernel has the map)
+    s->tile_xcd = xcd_kernel && opt_on(OPT_XCD_MAP);
     // the launch's blocks: its waves are the table's nw entries (rtx_camera_set pads the
     // tiles to whole 256-thread blocks), wpb per block. Dispatch position p (block p / wpb)
     // reads the entry of its slot (pixel_rc's xcd_block): the p-th dispatched wave renders
@@ -3855,6 +3864,11 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
         L.tlog = 0;
         L.xcd = opt_on(OPT_XCD_MAP) ? 1 : 0;
         L.redo = RedoList{nullptr, nullptr, nullptr};
+        // the current camera's tables, for the kernels that address them from the arguments
+        L.xs = s->kp.xs;
+        L.ys = s->kp.ys;
+        L.bin_objmask = s->kp.S.bin_objmask;
+        L.bin_shadow = s->kp.S.bin_shadow;
     }
     // the heavy tiles' chunks of a tile-mapped launch, just before it (the sample-parallel
     // and split kernels pass no pixel-in-tile and walk the lists). One pass serves every
@@ -3870,6 +3884,7 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
     JitSlot& rs = s->resolved[(out8 ? 8 : 0) | (cnt ? 4 : 0) | (jit ? 2 : 0) | (spp_mode ? 1 : 0)];
     if (!rs.done) {
         rs.block = jit_block(s->has_mesh, s->has_secondary, s->has_ext, spp_mode);
+        rs.xcd = opt_on(OPT_XCD_MAP);
         jit_render_kernel(s->device, s->view, s->kp, s->traits, s->has_mesh, s->has_secondary, s->has_ext, cnt, jit,
                           spp_mode, out8, s->jit_baked, rs);
         if (rs.pending && !opt_on(OPT_JIT_ASYNC) && !stream_capturing(st)) jit_poll(rs, true);
@@ -3879,6 +3894,7 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
     }
     if (rs.fn && jit_enabled()) {
         void* args[] = {(void*)&kp, (void*)&L};
+        if (!rs.xcd) L.xcd = 0;  // (a kernel compiled without the map keeps the blocks' own order)
         // whole-frame launches follow the measured tile schedule
         const bool whole = s->tile_sched != 0 && !spp_mode && L.row0 == 0 && L.nrows == s->kp.height &&
                            L.gstride == 0;
@@ -3887,11 +3903,11 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
         // (nor does a sequence launch: its frames differ in cost)
         const bool capturing = whole && (L.tstep != 0 || stream_capturing(st));
         if (whole && !capturing) {
-            if (int rc = tile_schedule(s, st, (uint32_t)rs.block / 64)) return rc;
+            if (int rc = tile_schedule(s, st, (uint32_t)rs.block / 64, rs.xcd)) return rc;
             L.tlog = s->tile_sched == 1;
         }
         if (whole) L.tperm = s->tile_sched == 3;
-        if (L.tperm) L.xcd = s->tile_xcd ? 1 : 0;
+        if (L.tperm) L.xcd = s->tile_xcd ? 1 : 0;  // (set only for a kernel with the map)
         if (int rc = heavy_pass(!spp_mode)) return rc;
         // (a one-wave-block kernel: the same waves in four times the blocks)
         const int64_t jblocks = rs.block == blk ? nblocks : nblocks * (blk / rs.block);  // (blk: 256 here)

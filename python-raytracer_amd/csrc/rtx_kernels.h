@@ -13,7 +13,24 @@
 
 namespace rtx {
 
-struct KParams {
+// The camera block: every wave-uniform value of the one-sample path at the head of KParams,
+// contiguous and 64-byte aligned, so a one-sample scene-specialized kernel fetches it with a
+// few wide scalar loads straight off the kernel argument, all issued together at the top of
+// render_body (no pointer between the argument and the values: dof0 / aa0 are copies of
+// dof_o[0] / aa_o[0], written by rtx_camera_set on every upload).
+struct alignas(64) KParams {
+    float pos[4], u[4], v[4], dw[4];
+    float focal, divisor, jscale, inv_divisor;
+    int32_t width, height, col0, ncols;
+    float dof0[4], aa0[4];  // dof_o[0][0..2], aa_o[0][0][0..2]
+    // RTX_PRIM_ORIGIN kernels (one sample, no jitter, static scene: every primary ray starts
+    // at aa_o[0]): its origin-only plane and sphere terms, computed by rtx_camera_set with
+    // closest_hit's fp32 operations (po_valid: computed)
+    int32_t po_valid, pad_h0, pad_h1, pad_h2;
+    float po_pnum[4];
+    float po_sq[16];
+    float po_soc[16][3];
+    // (the end of the camera block)
     SceneView S;
     // camera tables (device)
     cptr<float> xs;
@@ -22,11 +39,8 @@ struct KParams {
     cptr<float> aa_o;    // [n_dof][n_aa][3]
     cptr<float> times;   // [n_times] fp32; a sequence camera's [n_frames][n_times] (time_base)
     cptr<float> noise;   // replay jitter
-    float pos[4], u[4], v[4], dw[4];
-    float focal, divisor, jscale, inv_divisor;
     // n_frames: windows in `times` (host bookkeeping; the kernels index by Launch::tbase / tstep)
     int32_t div_pow2, n_frames, pad1, pad2;
-    int32_t width, height, col0, ncols;
     int32_t n_dof, n_aa, n_times, jitter;
     uint32_t seed_lo, seed_hi;
     // tools/wave_timeline.py only (kernels built with RTX_WAVE_LOG): per wave, its start
@@ -38,13 +52,6 @@ struct KParams {
     cptr<int32_t> tile_perm;
     unsigned int* tile_time;
     int32_t tile_n;
-    // RTX_PRIM_ORIGIN kernels (one sample, no jitter, static scene: every primary ray starts
-    // at aa_o[0]): its origin-only plane and sphere terms, computed by rtx_camera_set with
-    // closest_hit's fp32 operations (po_valid: computed)
-    int32_t po_valid;
-    float po_pnum[4];
-    float po_soc[16][3];
-    float po_sq[16];
 };
 
 template <bool COUNT>
@@ -80,8 +87,11 @@ __device__ __forceinline__ void flush_tally(const Tally& tl, unsigned long long*
 
 // scene.py:54-55: base_ray_direction and focal_point of pixel (column cc, reference row j).
 RTX_HD f3 pixel_focal(const KParams& P, int32_t cc, int j) {
-    const float fx = P.xs[cc];
-    const float fy = P.ys[j];
+    float fx = P.xs[cc];
+    float fy = P.ys[j];
+#if RTX_WAVE_HEAD  // both loads in flight before either is used
+    asm volatile("" : "+v"(fx), "+v"(fy));
+#endif
     // base_ray_direction = normalize(x * u + y * v - d * w)  (scene.py:54)
     const f3 bdir = normalize(sub(add(scale(ld3(P.u), fx), scale(ld3(P.v), fy)), ld3(P.dw)));
     return add(ld3(P.pos), scale(bdir, P.focal));  // scene.py:55
@@ -118,7 +128,11 @@ RTX_HD f3 jitter_rnd(const uint32_t w[4], int half) {
 // from the pair's block), else they are computed here.
 template <bool JIT>
 RTX_HD f3 sample_origin(const KParams& P, int32_t cc, int j, int kd, int ka, const f3* jr = nullptr) {
+#if RTX_WAVE_HEAD  // (one sample: the camera block's copy of aa_o[0])
+    f3 o = ld3(P.aa0);
+#else
     f3 o = ld3(P.aa_o + 3 * (kd * RTX_NAA(P) + ka));
+#endif
     if (JIT) {  // scene.py:63-65
         f3 rnd;
         if (RTX_JMODE(P) == RTX_JITTER_REPLAY) {
@@ -142,7 +156,10 @@ RTX_HD f3 sample_origin(const KParams& P, int32_t cc, int j, int kd, int ka, con
 // colour / (samples * dof_samples * len(motion_times)) (scene.py:73); for a power of two
 // the exact reciprocal multiply gives the identical correctly rounded result.
 RTX_HD float sample_mean(const KParams& P, float c) {
-#ifdef RTX_FIXED_DIVPOW2
+#if defined(RTX_FIXED_SAMPLES) && RTX_FIXED_NDOF * RTX_FIXED_NAA * RTX_FIXED_NTIMES == 1
+    (void)P;
+    return c;  // one sample: the divisor is 1 and c * 1.0f is c, bit for bit (no load before the store)
+#elif defined(RTX_FIXED_DIVPOW2)
     return RTX_FIXED_DIVPOW2 ? c * P.inv_divisor : c / P.divisor;
 #else
     return P.div_pow2 ? c * P.inv_divisor : c / P.divisor;
@@ -222,8 +239,13 @@ RTX_HD SceneView sample_scene(const SceneView& S0) {
 template <bool MESH, bool SEC, bool X, bool COUNT, bool JIT>
 RTX_HD void render_pixel(const KParams& P, float* fb, int32_t row0, int32_t rr, int32_t cc, Tally& tl,
                          const FrameStack& fs, const HStack& hs, int32_t bin = -1, int32_t tb = 0) {
+#ifdef RTX_FIXED_NCOLS  // (render_body's)
+    const int32_t ncols = RTX_FIXED_NCOLS;
+#else
+    const int32_t ncols = P.ncols;
+#endif
     if (RTX_PROBE(14)) {  // cost probe only: store a constant (launch + framebuffer write)
-        const int64_t p = (int64_t)rr * P.ncols + cc;
+        const int64_t p = (int64_t)rr * ncols + cc;
         put_channel(fb, 3 * p, 0.5f); put_channel(fb, 3 * p + 1, 0.25f); put_channel(fb, 3 * p + 2, 0.125f);
         return;
     }
@@ -254,7 +276,11 @@ RTX_HD void render_pixel(const KParams& P, float* fb, int32_t row0, int32_t rr, 
         if (RTX_RELOAD_RECORDS) asm volatile("" : "+v"(cc_k), "+v"(j_k));
 #endif
         const f3 focal = pixel_focal(P, cc_k, j_k);
+#if RTX_WAVE_HEAD  // (one sample: the camera block's copy of dof_o[0])
+        const f3 ddir = normalize(sub(focal, ld3(P.dof0)));  // scene.py:58
+#else
         const f3 ddir = normalize(sub(focal, ld3(P.dof_o + 3 * kd)));  // scene.py:58
+#endif
 #pragma unroll 1
         for (int ka = 0; ka < RTX_NAA(P); ++ka) {
             // the Philox block of samples (2m, 2m + 1), computed at the even one; the odd
@@ -286,7 +312,7 @@ RTX_HD void render_pixel(const KParams& P, float* fb, int32_t row0, int32_t rr, 
         colour = mk(c0, c1, c2 + c3 * 0.0f);
     }
 #endif
-    const int64_t p = (int64_t)rr * P.ncols + cc;
+    const int64_t p = (int64_t)rr * ncols + cc;
     put_channel(fb, 3 * p, colour.x);
     put_channel(fb, 3 * p + 1, colour.y);
     put_channel(fb, 3 * p + 2, colour.z);
@@ -415,6 +441,11 @@ struct Launch {
     // render_body_spp as the split passes' fallback (rtx_split.h): render only the listed
     // blocks (chains that found the record pool full), pixels from pix0 on
     RedoList redo;
+    // the current camera's per-pixel and per-tile tables (KParams::xs / ys, SceneView::
+    // bin_objmask / bin_shadow), filled at launch: a one-sample scene-specialized kernel
+    // addresses its tile's entries from the kernel arguments alone (render_body)
+    cptr<float> xs, ys;
+    cptr<uint32_t> bin_objmask, bin_shadow;
 };
 
 // This block's framebuffer (frame blockIdx.y of a batched launch; the only frame otherwise).
@@ -518,16 +549,38 @@ __host__ __device__ inline uint32_t xcd_block(uint32_t b, uint32_t nb, uint32_t 
     const uint32_t x = b & 7u, k = b >> 3;
     return (((k >> lg) << 3) + x) * g + (k & (g - 1u));
 }
+// B: the block size the kernel is launched with -- a constant of every kernel (kBlock), so
+// no wave fetches it from the dispatch packet. The grid size, which comes from the implicit
+// arguments (a scalar round trip at the start of every wave), is read only where its feature
+// is compiled in: the tile orders 1 and 2, and the XCD map (RTX_XCD_MAP: the precompiled
+// kernels, which take Launch::xcd at run time, and scene-specialized kernels compiled while
+// option xcd_map is set).
+#ifndef RTX_XCD_MAP
+#if defined(RTX_FIXED_COUNTS)
+#define RTX_XCD_MAP 0
+#else
+#define RTX_XCD_MAP 1
+#endif
+#endif
+template <int B>
 __device__ __forceinline__ PixelRC pixel_rc(int32_t ncols, int sub, uint32_t perm = 1, int32_t xcd = 0,
                                             const int32_t RTX_CONST* tperm = nullptr, int* tile = nullptr) {
+    constexpr uint32_t W = B >> 6;  // waves per block
     const int lane = threadIdx.x & 63;
-    const uint32_t blk = xcd ? xcd_block(blockIdx.x, gridDim.x, blockDim.x >> 6) : blockIdx.x;
-    int wave = __builtin_amdgcn_readfirstlane((int)((blk * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RTX_PPL + sub));
-    const uint32_t T = gridDim.x * (blockDim.x >> 6) * RTX_PPL;
+    uint32_t blk = blockIdx.x;
+#if RTX_XCD_MAP
+    if (xcd) blk = xcd_block(blockIdx.x, gridDim.x, W);
+#endif
+    int wave = __builtin_amdgcn_readfirstlane((int)((blk * W + (threadIdx.x >> 6)) * RTX_PPL + sub));
     if (RTX_TILE_SCHED && tperm != nullptr) wave = tperm[wave];
     if (tile) *tile = wave;
+#if RTX_TILE_ORDER == 1 || RTX_TILE_ORDER == 2
+    const uint32_t T = gridDim.x * W * RTX_PPL;
     if (RTX_TILE_ORDER == 1) wave = (int)T - 1 - wave;
     if (RTX_TILE_ORDER == 2) wave = (int)(((uint64_t)(uint32_t)wave * perm) % T);
+#else
+    (void)perm;
+#endif
     if (RTX_TILE == 0) {
         const int64_t p = (int64_t)wave * 64 + lane;
         const int32_t r = (int32_t)(p / ncols);
@@ -592,6 +645,30 @@ __device__ __forceinline__ void stage_records_lds(const SceneView& S) {
 #endif
 }
 
+// Four wave-uniform words the compiler must hold in scalar registers from here on: their
+// loads issue (and are waited for, once, with the others pinned beside them) where this
+// stands instead of sinking, each into the basic block of its first use.
+template <class T>
+__device__ __forceinline__ void pin_uniform(T& a, T& b, T& c, T& d) {
+    static_assert(sizeof(T) == 4, "32-bit scalars");
+    uint32_t w0 = __builtin_bit_cast(uint32_t, a), w1 = __builtin_bit_cast(uint32_t, b);
+    uint32_t w2 = __builtin_bit_cast(uint32_t, c), w3 = __builtin_bit_cast(uint32_t, d);
+    asm volatile("" : "+s"(w0), "+s"(w1), "+s"(w2), "+s"(w3));
+    a = __builtin_bit_cast(T, w0);
+    b = __builtin_bit_cast(T, w1);
+    c = __builtin_bit_cast(T, w2);
+    d = __builtin_bit_cast(T, w3);
+}
+
+template <class A, class B>  // (two wave-uniform pointers or 64-bit words)
+__device__ __forceinline__ void pin_uniform64(A& a, B& b) {
+    static_assert(sizeof(A) == 8 && sizeof(B) == 8, "64-bit scalars");
+    uint64_t x = (uint64_t)a, y = (uint64_t)b;
+    asm volatile("" : "+s"(x), "+s"(y));
+    a = (A)x;
+    b = (B)y;
+}
+
 // Wave timeline probe (experiment): the wave's start/end clock and where it ran.
 #if defined(RTX_WAVE_LOG) && defined(__HIP_DEVICE_COMPILE__)
 struct WaveClock {
@@ -628,6 +705,36 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
 #else
     const int32_t ncols = Pp->ncols;
 #endif
+#if RTX_WAVE_HEAD
+    // One-sample scene-specialized kernels: the frame parameters by value, read here, before
+    // anything else, so every scalar load of the wave's prologue goes out off the kernel
+    // arguments in one batch instead of one dependent round trip per use (each use sits in
+    // its own basic block, behind the previous one's wait). What stood behind a pointer of
+    // KParams comes from the camera block (dof0 / aa0: the only origins of a one-sample
+    // camera) or is addressed from Launch's copies of the table pointers.
+    KParams Q = *Pp;
+    Q.xs = L.xs;
+    Q.ys = L.ys;
+    Q.S.bin_objmask = L.bin_objmask;
+    Q.S.bin_shadow = L.bin_shadow;
+    if (!X) {
+        pin_uniform(Q.pos[0], Q.pos[1], Q.pos[2], Q.focal);
+        pin_uniform(Q.u[0], Q.u[1], Q.u[2], Q.dof0[0]);
+        pin_uniform(Q.v[0], Q.v[1], Q.v[2], Q.dof0[1]);
+        pin_uniform(Q.dw[0], Q.dw[1], Q.dw[2], Q.dof0[2]);
+        pin_uniform(Q.aa0[0], Q.aa0[1], Q.aa0[2], Q.S.ambient[0]);
+        pin_uniform(Q.height, Q.S.bins_x, Q.S.bins_on, Q.ncols);
+        pin_uniform64(Q.xs, Q.ys);
+        pin_uniform64(Q.S.bin_objmask, Q.S.bin_shadow);
+    }
+    float* fbp = frame_fb(L);
+    int64_t fbw = L.fstride;  // (pinned beside it only)
+    if (!X) pin_uniform64(fbp, fbw);
+    const KParams& P = X ? *Pp : Q;  // (the hierarchy / texture kernels keep the pointer)
+#else
+    const KParams& P = *Pp;
+    float* const fbp = frame_fb(L);
+#endif
     Tally tl = {};
     // secondary-ray frames: [frame][word][thread] in LDS (40 KB per 256-thread block; 30 KB
     // with RTX_FRAME_MATBITS)
@@ -644,17 +751,21 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
 #endif
     for (int sub = 0; sub < RTX_PPL; ++sub) {
 #if RTX_TILE_SCHED && defined(__HIP_DEVICE_COMPILE__)
-        const PixelRC px = pixel_rc(ncols, sub, L.perm, L.xcd, L.tperm ? Pp->tile_perm : nullptr, &tile);
+        const PixelRC px = pixel_rc<B>(ncols, sub, L.perm, L.xcd, L.tperm ? Pp->tile_perm : nullptr, &tile);
 #else
-        const PixelRC px = pixel_rc(ncols, sub, L.perm, L.xcd);
+        const PixelRC px = pixel_rc<B>(ncols, sub, L.perm, L.xcd);
 #endif
         const bool active = px.r < L.nrows && px.c < ncols;
         any_active = any_active || active;
         // primary-ray face bin of the wave's 8x8 tile (its top-left pixel)
-        const int32_t bin = RTX_TILE == 1 ? primary_bin(Pp->S, image_row(L, px.r & ~7), px.c & ~7) : -1;
+        const int32_t bin = RTX_TILE == 1 ? primary_bin(P.S, image_row(L, px.r & ~7), px.c & ~7) : -1;
+#if RTX_WAVE_HEAD && RTX_TILE == 1 && RTX_PRIMARY_BINS
+        // the tile's object mask, fetched here and handed down by value (SceneView::tile_objmask)
+        if (!X && bin >= 0) Q.S.tile_objmask = Q.S.bin_objmask[wave_uniform(bin)];
+#endif
         // render_pixel's image row is row0 + rr: pass the image row of px.r as that sum
         if (active)
-            render_pixel<MESH, SEC, X, COUNT, JIT>(*Pp, frame_fb(L), image_row(L, px.r) - px.r, px.r, px.c, tl, fs, hs, bin,
+            render_pixel<MESH, SEC, X, COUNT, JIT>(P, fbp, image_row(L, px.r) - px.r, px.r, px.c, tl, fs, hs, bin,
                                                    tb);
     }
     flush_tally<COUNT>(tl, L.counters, any_active);
@@ -859,7 +970,7 @@ __global__ __launch_bounds__(kBlock<X>) void k_aov(const KParams* __restrict__ P
     const HStack hs{hstack + threadIdx.x, B};
     const KParams& P = *Pp;
     const int32_t ncols = P.ncols;
-    const PixelRC px = pixel_rc(ncols, 0);
+    const PixelRC px = pixel_rc<B>(ncols, 0);
     if (!(px.r < L.nrows && px.c < ncols)) return;
     const int32_t bin = RTX_TILE == 1 ? primary_bin(P.S, L.row0 + (px.r & ~7), px.c & ~7) : -1;
     const int j = P.height - 1 - (L.row0 + px.r);  // reference row index (y grows upward)

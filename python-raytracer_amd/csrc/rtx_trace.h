@@ -374,7 +374,22 @@ struct SceneView {
     // 0-15) and boxes (16-31) that can occlude light's shadow ray from a camera ray's hit
     // point in that 8x8 bin (bin_objmask's layout and bins); null: every object is tested
     cptr<uint32_t> bin_shadow;
+    // One-sample scene-specialized kernels (rtx_kernels.h render_body, RTX_WAVE_HEAD): the
+    // wave's tile's word of bin_objmask, read at the top of the kernel and handed down by
+    // value; zero in memory
+    uint32_t tile_objmask, pad14, pad15, pad16;
 };
+
+// Kernels whose render_body takes the frame parameters by value at its top (rtx_kernels.h): the
+// one-sample scene-specialized ones. Multi-sample kernels re-read them per sample on purpose
+// (RTX_RELOAD_RECORDS), and the precompiled kernels keep the pointer.
+#ifndef RTX_WAVE_HEAD
+#if defined(RTX_FIXED_SAMPLES) && defined(__HIP_DEVICE_COMPILE__)
+#define RTX_WAVE_HEAD (RTX_FIXED_NDOF * RTX_FIXED_NAA * RTX_FIXED_NTIMES == 1)
+#else
+#define RTX_WAVE_HEAD 0
+#endif
+#endif
 
 // Kernels that read SceneView::bin_shadow. Scene-specialized kernels do only when their
 // camera has the table (rtx_api.hip jit_spec defines it then); everything else checks the
@@ -2197,6 +2212,8 @@ RTX_HD Hit closest_hit(const SceneView& S, f3 o, f3 d, float time, Tally& tl, co
         // misses the tile (rtx_api.hip primary_bins; wave-uniform)
 #if defined(RTX_PRIMARY_BINS) && !RTX_PRIMARY_BINS
         constexpr uint32_t omask = ~0u;
+#elif RTX_WAVE_HEAD  // (the tile's word, by value: render_body read it)
+        const uint32_t omask = bin < 0 ? ~0u : X ? S.bin_objmask[wave_uniform(bin)] : S.tile_objmask;
 #else
         const uint32_t omask = bin >= 0 ? S.bin_objmask[wave_uniform(bin)] : ~0u;
 #endif
