@@ -20,6 +20,8 @@
  *                         (provided/geometry/__init__.py:47-48, provided/scene.py:86-94)
  *   rtx_occluded       <- the Geometry.shadow_intersect plugin ABI + any-hit loop
  *                         (provided/geometry/__init__.py:50-51, provided/scene.py:160-164)
+ *   rtx_cast_rays      <- Scene.cast_ray for caller-built rays, batched
+ *                         (provided/scene.py:81-116, :140-187, :189-209)
  *   rtx_fb_to_rgb8     <- main.py's rot90 + truncating uint8 conversion
  *                         (provided/main.py:31-33; rot90 is the fb's row order)
  *
@@ -281,6 +283,43 @@ int rtx_intersect(rtx_scene* scene, int64_t n, const float* ray_o_dev, const flo
 /* Any-hit shadow test of n rays against every object with per-ray t_max (fp64). */
 int rtx_occluded(rtx_scene* scene, int64_t n, const float* ray_o_dev, const float* ray_d_dev,
                  const double* t_max_dev, double time, uint8_t* occluded_dev, void* hip_stream);
+
+/* Colours of caller-built rays: Scene.cast_ray (provided/scene.py:81-116 -- closest hit, shadow
+ * rays, lighting, the reflect / refract chain of up to 10 casts, the per-level clamp) as a
+ * batched call; with rtx_intersect and rtx_occluded the third entry of the plugin ABI. For a
+ * camera the reference lacks (panorama, orthographic, a probe at a surface point), a moving
+ * camera without a camera upload per frame, a reflection pass from rtx_render_aov's position /
+ * normal buffers. Works before rtx_camera_set, like rtx_intersect, and uses nothing of the
+ * camera: none of its bins, shadow bins or self-test tables, which hold for its own rays only.
+ *   ray_o_dev, ray_d_dev  n rays, SoA fp32 [3][n] (rtx_intersect's layout). Directions are used
+ *                         as given: the reference does not normalise them (scene.py:176's half
+ *                         vector reads the ray's own direction).
+ *   times                 host array of n_times motion times, 1 <= n_times <= RTX_CAST_MAX_TIMES,
+ *                         each finite; cast to fp32 like a camera's. Every ray is cast at every
+ *                         time, with the same origin and direction.
+ *   group                 rays per output colour, >= 1 and a divisor of n (group * n_times
+ *                         below 2^31).
+ *   rgb_dev               fp32 [n / group][3], pixel-major like the framebuffer (rtx_fb_to_rgb8
+ *                         applies). rgb[j] = (c_0 + c_1 + ... + c_{S-1}) / fl32(S), S = group *
+ *                         n_times, where c_s is the clamped fp32 colour of ray j * group +
+ *                         s / n_times at times[s % n_times] (time fastest: the loop nest of one
+ *                         pixel, scene.py:57-69), added in that order in fp32 from +0 and divided
+ *                         once, correctly rounded: what rtx_render stores for a pixel whose
+ *                         samples are these rays. Every c_s is bit-identical to the reference's.
+ *   counters_dev          NULL, or RTX_COUNTERS tallies in rtx_render's layout, accumulated.
+ * Asynchronous on the stream. A scene with hierarchy nodes gets their boxes for
+ * [min(times), max(times)] uploaded in stream order by the call (as rtx_intersect does for its
+ * one time), so calls on one scene must be stream-ordered, and only a scene without hierarchy
+ * nodes may have the call captured into a HIP graph. RTX_ERR_INVALID for a null scene, n < 0,
+ * null rays or a null output with n > 0, group < 1 or not a divisor of n, n_times outside
+ * [1, RTX_CAST_MAX_TIMES] or null times, a non-finite time (as fp32), group * n_times >= 2^31,
+ * or more than 2^31 - 1 blocks; all checked before any HIP call. RTX_ERR_STATE when the scene
+ * lives on another device than the current one. n == 0 is RTX_OK and launches nothing.
+ * rtx_last_kernel is left as it is. */
+#define RTX_CAST_MAX_TIMES 64
+int rtx_cast_rays(rtx_scene* scene, int64_t n, const float* ray_o_dev, const float* ray_d_dev,
+                  const double* times, int32_t n_times, int32_t group, float* rgb_dev,
+                  unsigned long long* counters_dev, void* hip_stream);
 
 /* out_dev[i] = (uint8)(fb_dev[i] * 255.0) in fp64 with truncation (main.py:33). */
 int rtx_fb_to_rgb8(const float* fb_dev, uint8_t* out_dev, int64_t n_values, void* hip_stream);

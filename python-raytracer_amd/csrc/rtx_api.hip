@@ -10,6 +10,8 @@
 //                 buffers (depth, normal, position, albedo, object and material ids)
 //   k_intersect   closest hit of SoA rays (Geometry.intersect + min, scene.py:86-94)
 //   k_occluded    shadow any-hit of SoA rays (Geometry.shadow_intersect, scene.py:160-164)
+//   k_cast_rays   one work-item per sample of caller-built SoA rays: cast_ray's colour, the
+//                 samples of an output added in order (Scene.cast_ray, scene.py:81-116)
 //   k_to_rgb8     (v * 255.0) truncated to uint8 (main.py:33)
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -3988,12 +3990,11 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
 }  // namespace
 
 namespace {
-// The scene view for one motion time (hierarchy bounds uploaded in stream order).
-int view_at(rtx_scene* s, double time, hipStream_t stream, SceneView& v) {
+// The scene view for the motion times [tlo, thi] (hierarchy bounds uploaded in stream order).
+int view_at(rtx_scene* s, float tlo, float thi, hipStream_t stream, SceneView& v) {
     v = s->view;
     if (s->h_nodes.empty()) return RTX_OK;
-    const float t = (float)time;
-    s->h_bounds_abi = split_bounds(compute_bounds(s->h_nodes, s->h_objs, s->h_tris, t, t));
+    s->h_bounds_abi = split_bounds(compute_bounds(s->h_nodes, s->h_objs, s->h_tris, tlo, thi));
     RTX_HIP(hipMemcpyAsync(s->d_bounds_abi, s->h_bounds_abi.data(), sizeof(DBox) * s->h_bounds_abi.size(),
                            hipMemcpyHostToDevice, stream));
     bind_boxes(v, (const DBox*)s->d_bounds_abi, s->h_nodes.size());
@@ -4006,7 +4007,7 @@ int rtx_intersect(rtx_scene* s, int64_t n, const float* ro, const float* rd, dou
     if (!s || n < 0 || (n > 0 && (!ro || !rd))) return fail(RTX_ERR_INVALID, "rtx_intersect: bad argument");
     if (n == 0) return RTX_OK;
     SceneView view;
-    int rc = view_at(s, time, (hipStream_t)stream, view);
+    int rc = view_at(s, (float)time, (float)time, (hipStream_t)stream, view);
     if (rc) return rc;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     const size_t lds = s->has_ext ? (size_t)s->hlevels * 9 * sizeof(float) * 256 : 0;
@@ -4062,7 +4063,7 @@ int rtx_occluded(rtx_scene* s, int64_t n, const float* ro, const float* rd, cons
     if (!s || n < 0 || (n > 0 && (!ro || !rd || !tmax || !occ))) return fail(RTX_ERR_INVALID, "rtx_occluded: bad argument");
     if (n == 0) return RTX_OK;
     SceneView view;
-    int rc = view_at(s, time, (hipStream_t)stream, view);
+    int rc = view_at(s, (float)time, (float)time, (hipStream_t)stream, view);
     if (rc) return rc;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     const size_t lds = s->has_ext ? (size_t)s->hlevels * 9 * sizeof(float) * 256 : 0;
@@ -4071,6 +4072,73 @@ int rtx_occluded(rtx_scene* s, int64_t n, const float* ro, const float* rd, cons
     if (s->has_mesh) { if (s->has_ext) RTX_OCC(true, true); else RTX_OCC(true, false); }
     else { if (s->has_ext) RTX_OCC(false, true); else RTX_OCC(false, false); }
 #undef RTX_OCC
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+}  // extern "C"
+
+namespace rtx {
+// Weak references here only: a build of this file without the two kernel units (the tests'
+// host emulation, which launches no kernel and does not emulate k_cast_rays) still links and
+// loads; rtx_cast_rays finds them null there and reports RTX_ERR_UNSUPPORTED.
+__attribute__((weak)) hipError_t launch_cast_ext_m0(int, unsigned, size_t, hipStream_t, const SceneView&, const CastLaunch&);
+__attribute__((weak)) hipError_t launch_cast_ext_m1(int, unsigned, size_t, hipStream_t, const SceneView&, const CastLaunch&);
+}  // namespace rtx
+
+extern "C" {
+
+int rtx_cast_rays(rtx_scene* s, int64_t n, const float* ro, const float* rd, const double* times, int32_t n_times,
+                  int32_t group, float* rgb_dev, unsigned long long* counters_dev, void* stream) {
+    if (!s) return fail(RTX_ERR_INVALID, "rtx_cast_rays: null scene");
+    if (n < 0) return fail(RTX_ERR_INVALID, "rtx_cast_rays: n < 0");
+    if (n > 0 && (!ro || !rd || !rgb_dev)) return fail(RTX_ERR_INVALID, "rtx_cast_rays: null rays or null output");
+    if (group < 1 || n % group != 0)
+        return fail(RTX_ERR_INVALID, "rtx_cast_rays: group " + std::to_string(group) + " must be >= 1 and divide n = " +
+                                         std::to_string(n));
+    if (!times || n_times < 1 || n_times > RTX_CAST_MAX_TIMES)
+        return fail(RTX_ERR_INVALID, "rtx_cast_rays: 1 to " + std::to_string(RTX_CAST_MAX_TIMES) +
+                                         " motion times, got " + std::to_string(n_times));
+    CastLaunch L{ro, rd, rgb_dev, counters_dev, n, group, n_times, {}};
+    for (int k = 0; k < n_times; ++k) {
+        L.times[k] = (float)times[k];
+        if (!std::isfinite(times[k]) || !std::isfinite(L.times[k]))
+            return fail(RTX_ERR_INVALID, "rtx_cast_rays: motion time " + std::to_string(k) + " is not finite");
+    }
+    const int64_t ns = (int64_t)group * n_times;  // samples per output
+    if (ns > 0x7fffffff) return fail(RTX_ERR_INVALID, "rtx_cast_rays: group * n_times >= 2^31");
+    const int blk = s->has_ext ? kBlock<true> : kBlock<false>;
+    const int ppb = spp_pixels_per_block((int)ns, blk);  // outputs per block (k_cast_rays)
+    const int64_t nblocks = (n / group + ppb - 1) / ppb;
+    if (nblocks > 0x7fffffff) return fail(RTX_ERR_INVALID, "rtx_cast_rays: launch too large");
+    if (n == 0) return RTX_OK;
+    if (s->has_ext && !(s->has_mesh ? launch_cast_ext_m1 : launch_cast_ext_m0))
+        return fail(RTX_ERR_UNSUPPORTED, "rtx_cast_rays: this build holds no hierarchy/texture kernels");
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != s->device)
+        return fail(RTX_ERR_STATE, "rtx_cast_rays: the scene lives on device " + std::to_string(s->device) +
+                                       ", the current device is " + std::to_string(cur));
+    // the scene-level view, with the hierarchy boxes of the call's time range
+    SceneView view;
+    hipStream_t st = (hipStream_t)stream;
+    const auto mm = std::minmax_element(L.times, L.times + n_times);
+    if (int rc = view_at(s, *mm.first, *mm.second, st, view)) return rc;
+    const bool cnt = counters_dev != nullptr;
+    if (s->has_ext) {  // precompiled in rtx_kern_ext_m{0,1}.hip
+        const int sel = (s->has_secondary ? 8 : 0) | (cnt ? 2 : 0);
+        const size_t lds = (size_t)s->hlevels * 9 * sizeof(float) * kBlock<true>;
+        RTX_HIP(s->has_mesh ? launch_cast_ext_m1(sel, (unsigned)nblocks, lds, st, view, L)
+                            : launch_cast_ext_m0(sel, (unsigned)nblocks, lds, st, view, L));
+        return RTX_OK;
+    }
+#define RTX_CAST(M, S, C) \
+    hipLaunchKernelGGL((k_cast_rays<M, S, false, C>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0, st, view, L)
+#define RTX_CAST_C(M, S) \
+    do { if (cnt) RTX_CAST(M, S, true); else RTX_CAST(M, S, false); } while (0)
+    if (s->has_mesh) { if (s->has_secondary) RTX_CAST_C(true, true); else RTX_CAST_C(true, false); }
+    else { if (s->has_secondary) RTX_CAST_C(false, true); else RTX_CAST_C(false, false); }
+#undef RTX_CAST_C
+#undef RTX_CAST
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

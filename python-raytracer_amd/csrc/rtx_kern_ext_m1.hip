@@ -50,4 +50,14 @@ hipError_t launch_split_m1(int sel, int pass, const RenderLaunch& r, const Launc
     return hipGetLastError();
 }
 
+hipError_t launch_cast_ext_m1(int sel, unsigned nblocks, size_t lds_bytes, hipStream_t stream, const SceneView& S,
+                              const CastLaunch& L) {
+    constexpr int B = kBlock<true>;
+#define RTX_CAST_X(SEC, C) hipLaunchKernelGGL((k_cast_rays<true, SEC, true, C>), dim3(nblocks), dim3(B), lds_bytes, stream, S, L)
+    if (sel & 8) { if (sel & 2) RTX_CAST_X(true, true); else RTX_CAST_X(true, false); }
+    else { if (sel & 2) RTX_CAST_X(false, true); else RTX_CAST_X(false, false); }
+#undef RTX_CAST_X
+    return hipGetLastError();
+}
+
 }  // namespace rtx

@@ -1003,6 +1003,104 @@ __global__ __launch_bounds__(kBlock<X>) void k_aov(const KParams* __restrict__ P
     }
 }
 
+// The per-call block of rtx_cast_rays: n caller-built rays as SoA fp32 [3][n] (rtx_intersect's
+// layout), the motion times by value, and the output, fp32 [n / group][3].
+struct CastLaunch {
+    const float* ro;
+    const float* rd;
+    float* rgb;
+    unsigned long long* counters;
+    int64_t n;
+    int32_t group, n_times;
+    float times[RTX_CAST_MAX_TIMES];
+};
+
+// scene.py:81-116 for caller-built rays (rtx_cast_rays): one lane traces one sample. Output j
+// is the mean of S = group * n_times samples; its sample s is ray j * group + s / n_times at
+// times[s % n_times] (time fastest: scene.py:57-69's loop nest for one pixel). The mapping is
+// render_block_spp's: the B lanes of a block trace the samples of PPB = B / S consecutive
+// outputs, or those of one output in ceil(S / B) rounds; each lane parks its colour in LDS
+// and one owner lane per (output, channel) adds the samples in order from +0 and divides
+// once -- render_pixel's fp32 sums. S == 1 (PPB = B) stores the lane's own colour: c / 1.0f
+// is c; no LDS traffic, no barrier. The parking words are the lane's own words of frame 0
+// of its FrameStack ([frame][word][thread]: a lane's column is its own, and its frames are
+// dead once its cast_ray has returned), so secondary-ray variants need no LDS beside the
+// frames. S is the scene-level view (rtx_scene_create's): no primary bins, shadow bins,
+// plane self tests or directional shadow grids -- those hold for the camera's rays only --
+// so cast_ray's level-0 self object can skip nothing (occluded reads it only beside
+// SceneView::plane_self and DSGrid::self_boxes, both absent: null and dsg_on = 0).
+// Every thread reaches every barrier: inactive lanes (ragged last block, lp >= PPB) only
+// skip the trace.
+template <bool MESH, bool SEC, bool X, bool COUNT>
+__global__ RTX_RENDER_BOUNDS(MESH, SEC, X) void k_cast_rays(const SceneView S, const CastLaunch L) {
+    constexpr int B = kBlock<X>;
+    static_assert(kFrameWords >= 3, "a lane parks its colour in three words of its frame 0");
+    __shared__ float lds[SEC ? kFrameLds * kFrameWords * B : 3 * B];
+    extern __shared__ float hstack[];  // X: [level][9][thread] (dynamic size)
+    const FrameStack fs{lds + threadIdx.x, B};
+    const HStack hs{hstack + threadIdx.x, B};
+    const int tid = threadIdx.x;
+    const int G = L.group, T = L.n_times;
+    const int ns = G * T;  // samples per output (the host bounds it by 2^31 - 1)
+    const bool single = ns == 1;
+    const int PPB = spp_pixels_per_block(ns, B);
+    const int rounds = ns <= B ? 1 : (int)(((int64_t)ns + B - 1) / B);
+    const float rS = 1.0f / (float)ns;
+    const int64_t nout = L.n / G;
+    const int64_t out0 = (int64_t)blockIdx.x * PPB;
+    Tally tl = {};
+    bool any_active = false;
+    float acc = 0.0f;  // rounds > 1 (one output per block): lane ch < 3 sums channel ch
+    for (int rd = 0; rd < rounds; ++rd) {
+        const uint32_t flat = (uint32_t)rd * B + tid;  // the block's sample index
+        int lp, s;
+        if (ns < B) {
+            lp = udiv_small((int)flat, ns, rS, s);
+        } else {  // one output per block: its samples in order
+            lp = flat < (uint32_t)ns ? 0 : 1;
+            s = (int)flat;
+        }
+        const int64_t j = out0 + lp;
+        const bool active = lp < PPB && j < nout;
+        f3 c = mk(0.0f, 0.0f, 0.0f);
+        if (active) {
+            any_active = true;
+            const uint32_t g = T == 1 ? (uint32_t)s : (uint32_t)s / (uint32_t)T;
+            const int kt = T == 1 ? 0 : (int)((uint32_t)s - g * (uint32_t)T);
+            const int64_t i = j * G + g;
+            const f3 o = mk(L.ro[i], L.ro[L.n + i], L.ro[2 * L.n + i]);
+            const f3 d = mk(L.rd[i], L.rd[L.n + i], L.rd[2 * L.n + i]);
+            c = cast_ray<MESH, SEC, X, COUNT>(S, o, d, L.times[kt], tl, fs, hs);
+        }
+        if (single) {
+            if (active) put3(L.rgb, j, c);
+            continue;
+        }
+        lds[tid] = c.x;
+        lds[B + tid] = c.y;
+        lds[2 * B + tid] = c.z;
+        __syncthreads();
+        if (rounds == 1) {  // (output, channel) pairs, each summed in order by one lane
+            for (int q = tid; q < 3 * PPB; q += B) {
+                const int pp = q / 3, ch = q - 3 * pp;
+                if (out0 + pp < nout) {
+                    const float* src = lds + ch * B + pp * ns;
+                    float a = 0.0f;
+                    for (int k = 0; k < ns; ++k) a += src[k];
+                    L.rgb[3 * (out0 + pp) + ch] = a / (float)ns;
+                }
+            }
+        } else if (tid < 3) {  // this round's samples of the block's output
+            const int hi = min(ns - rd * B, B);
+            const float* src = lds + tid * B;
+            for (int k = 0; k < hi; ++k) acc += src[k];
+        }
+        __syncthreads();  // the words are frames again in the next round
+    }
+    if (rounds > 1 && tid < 3 && out0 < nout) L.rgb[3 * out0 + tid] = acc / (float)ns;
+    flush_tally<COUNT>(tl, L.counters, any_active);
+}
+
 #if !defined(RTX_EXT_TU)  // defined once, in rtx_api.hip
 // The heavy tiles' chunks (one wave per chunk, launched as one-wave blocks), before the
 // render kernel: items (bin, chunk). A launch of rows (row0, nrows) or 8-row groups

@@ -26,4 +26,13 @@ hipError_t launch_render_ext_m1(int sel, const RenderLaunch& r, const Launch& L)
 struct SplitBuf;
 hipError_t launch_split_m0(int sel, int pass, const RenderLaunch& r, const Launch& L, const SplitBuf& sb);
 hipError_t launch_split_m1(int sel, int pass, const RenderLaunch& r, const Launch& L, const SplitBuf& sb);
+
+// k_cast_rays (rtx_cast_rays) of the hierarchy/texture variants: nblocks one-wave blocks with
+// lds_bytes of dynamic LDS. sel: (SEC ? 8 : 0) | (COUNT ? 2 : 0).
+struct SceneView;
+struct CastLaunch;
+hipError_t launch_cast_ext_m0(int sel, unsigned nblocks, size_t lds_bytes, hipStream_t stream, const SceneView& S,
+                              const CastLaunch& L);
+hipError_t launch_cast_ext_m1(int sel, unsigned nblocks, size_t lds_bytes, hipStream_t stream, const SceneView& S,
+                              const CastLaunch& L);
 }  // namespace rtx

@@ -27,6 +27,7 @@ RTX_BV_AABB, RTX_BV_SPHERE = 0, 1
 RTX_JITTER_OFF, RTX_JITTER_PHILOX, RTX_JITTER_REPLAY = 0, 1, 2
 RTX_COUNTERS = 16
 RTX_CNT_SHADOW, RTX_CNT_SHADE, RTX_CNT_TRI = 10, 11, 12
+RTX_CAST_MAX_TIMES = 64  # motion times of one rtx_cast_rays call
 
 _f3 = C.c_float * 3
 
@@ -92,7 +93,7 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_scene_create", "rtx_scene_d
            "rtx_render_rgb8", "rtx_render_groups_rgb8", "rtx_last_kernel", "rtx_render_frames",
            "rtx_render_groups_frames", "rtx_jit_modules", "rtx_set_option", "rtx_get_option", "rtx_option_name",
            "rtx_graph_launch", "rtx_jit_wait", "rtx_render_sequence", "rtx_render_groups_sequence",
-           "rtx_render_aov"]
+           "rtx_render_aov", "rtx_cast_rays"]
 
 
 def load():
@@ -123,6 +124,8 @@ def load():
                 f.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, vp]
         if hasattr(lib, "rtx_render_aov"):
             lib.rtx_render_aov.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(lib, "rtx_cast_rays"):
+            lib.rtx_cast_rays.argtypes = [vp, C.c_int64, vp, vp, _pd, C.c_int32, C.c_int32, vp, vp, vp]
         lib.rtx_group_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.rtx_group_rows.restype = C.c_int32
         lib.rtx_intersect.argtypes = [vp, C.c_int64, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]

@@ -21,6 +21,12 @@ a %d pattern in the name, e.g. frame%03d.png).
 
 Besides the image, the first-hit feature buffers of Scene.render_aovs (no reference
 counterpart; default: all six) as (H, W) or (H, W, 3) arrays of one .npz file.
+
+    python -m rtx.main --infile S.json --outfile pano.png --panorama W H
+
+An equirectangular W x H panorama about the scene's camera position (no reference
+counterpart: rtx.panorama_rays shaded by Scene.cast_rays_device at the camera's motion times),
+in place of the camera's image.
 """
 import argparse
 import json
@@ -50,7 +56,16 @@ def parse(argv=None):
                    help="also write the first-hit feature buffers (Scene.render_aovs) to this .npz file")
     p.add_argument("--aov-names", type=str, nargs="+", default=None, metavar="NAME",
                    help="the buffers to write (default: depth normal position albedo object material)")
+    p.add_argument("--panorama", type=int, nargs=2, default=None, metavar=("W", "H"),
+                   help="write an equirectangular W x H panorama about the camera position instead of its image")
     args = p.parse_args(argv)
+    if args.panorama is not None:
+        if args.distributed or args.frames is not None or args.aovs is not None or args.subimage is not None \
+                or args.tasks is not None:
+            p.error("--panorama writes one whole image on one GPU: it cannot be combined with --distributed, "
+                    "--frames, --aovs or --subimage / --tasks")
+        if min(args.panorama) < 1:
+            p.error("--panorama takes a width and a height >= 1")
     if args.aovs is not None:
         if args.distributed:
             p.error("--aovs renders on one GPU: it cannot be combined with --distributed")
@@ -123,6 +138,17 @@ def write_aovs(sc, args):
     return args.aovs
 
 
+def render_panorama(sc, width, height):
+    """The panorama's PNG bytes, uint8 (height, width, 3): panorama_rays shaded at the camera's
+    motion times, converted on the device like a render (rtx_fb_to_rgb8)."""
+    import torch
+    from .scene import fb_to_rgb8, panorama_rays
+    o, d = panorama_rays(sc.vc, width, height)
+    o, d = (torch.as_tensor(numpy.ascontiguousarray(a.T)).cuda() for a in (o, d))
+    fb = sc.cast_rays_device(o, d, [float(t) for t in sc.vc.motion_times])
+    return fb_to_rgb8(fb.view(height, width, 3)).cpu().numpy()
+
+
 def _scene(args):
     from .scene_parser import load_scene
     if args.resolution is None and args.spp is None:
@@ -157,6 +183,9 @@ def main(argv=None):
         dist.destroy_process_group()
         return
     full_scene = _scene(args)
+    if args.panorama is not None:
+        Image.fromarray(render_panorama(full_scene, *args.panorama)).save(args.outfile)
+        return
     if args.frames is not None:
         render_frames_to_files(full_scene, args)
         return

@@ -122,6 +122,25 @@ def sequence_windows(windows):
     return rows
 
 
+def panorama_rays(vc, width, height):
+    """An equirectangular panorama about the camera position, a camera the reference lacks,
+    as rays for Scene.cast_rays: (origins, directions), numpy float32 [height * width, 3],
+    row 0 at the top, pixel-major. Pixel (r, c) looks along
+    d = sin(theta) (cos(phi) (-w) + sin(phi) u) + cos(theta) v with theta = pi (r + 0.5) / height
+    and phi = 2 pi (c + 0.5) / width - pi: the image centre looks where the camera does, its
+    top along the camera's up. Evaluated in fp64 from the camera's u, v, w and rounded once to
+    fp32; the origin is the fp32 camera position."""
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError("a panorama needs width >= 1 and height >= 1")
+    u, v, w = (np.asarray(x, np.float32).astype(np.float64).reshape(3) for x in (vc.u, vc.v, vc.w))
+    theta = (math.pi * (np.arange(height, dtype=np.float64) + 0.5) / height)[:, None, None]
+    phi = (2.0 * math.pi * (np.arange(width, dtype=np.float64) + 0.5) / width - math.pi)[None, :, None]
+    d = np.sin(theta) * (np.cos(phi) * -w + np.sin(phi) * u) + np.cos(theta) * v
+    o = np.broadcast_to(np.asarray(vc.position, np.float32).reshape(3), d.shape)
+    return np.ascontiguousarray(o).reshape(-1, 3), d.astype(np.float32).reshape(-1, 3)
+
+
 _GENERATION = itertools.count(1)
 
 
@@ -571,6 +590,121 @@ class Scene:
         N.call("rtx_occluded", nat.h, n, vp(o.data_ptr()), vp(d.data_ptr()), vp(tm.data_ptr()), float(time),
                vp(occ.data_ptr()), vp(torch.cuda.current_stream().cuda_stream))
         return occ.cpu().numpy().astype(bool)
+
+    # ------------------------------------------------------------------ shading caller-built rays
+    def camera_rays(self, subimage=0, tasks=1, device=False):
+        """The reference camera's sample rays of the strip (scene.py:54-65), in fp32 from
+        camera_tables: (origins [n, 3], directions [n, 3], group) as numpy float32 arrays,
+        ordered image row (row 0 = top), column, DOF origin, AA origin, with
+        group = dof_samples * samples rays per pixel; replayed jitter (jitter_noise) moves
+        the origins as scene.py:63-65 does. ``device=True``: the rays as contiguous float32
+        CUDA tensors [3, n] instead, what cast_rays_device takes -- then
+        ``cast_rays_device(o, d, vc.motion_times, group).view(H, W, 3)`` is
+        ``render_device(subimage, tasks)`` bit for bit. ValueError for Philox jitter, whose
+        draws exist only on the device."""
+        if self.jitter and self.jitter_noise is None:
+            raise ValueError("camera_rays needs replayed jitter (jitter_noise): Philox draws exist only on the device")
+        t = self.camera_tables(subimage, tasks)
+        vc = self.vc
+        f32 = np.float32
+        H, W, nd, na = vc.height, t["ncols"], vc.dof_samples, self.samples
+        u, v, w = (np.asarray(x, f32) for x in (vc.u, vc.v, vc.w))
+        xs, ys = t["xs"], t["ys"][::-1]  # image row r is the reference's row H - 1 - r
+        bdir = F.normalize((xs[None, :, None] * u + ys[:, None, None] * v) - w * f32(vc.d))  # scene.py:54
+        focal = np.asarray(vc.position, f32) + bdir * f32(vc.focal_length)                    # scene.py:55
+        dof = t["dof"].astype(f32).reshape(nd, 3)
+        d = F.normalize(focal[:, :, None, :] - dof[None, None])                               # scene.py:58
+        d = np.broadcast_to(d[:, :, :, None, :], (H, W, nd, na, 3))
+        o = np.broadcast_to(t["aa"].astype(f32).reshape(nd, na, 3), (H, W, nd, na, 3))        # scene.py:60-61
+        if self.jitter:                                                                       # scene.py:63-65
+            need = W * H * nd * na * 3
+            noise = np.asarray(self.jitter_noise, np.float64).ravel()
+            if noise.size < need:
+                raise ValueError("jitter_noise too short: %d < %d" % (noise.size, need))
+            # the reference draws per column, then per row from the bottom
+            nz = noise[:need].astype(f32).reshape(W, H, nd, na, 3).transpose(1, 0, 2, 3, 4)[::-1]
+            o = o + F.normalize(nz) * f32(t["jscale"])
+        o = np.ascontiguousarray(o, f32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, f32).reshape(-1, 3)
+        if device:
+            return (torch.as_tensor(np.ascontiguousarray(o.T)).cuda(), torch.as_tensor(np.ascontiguousarray(d.T)).cuda(),
+                    nd * na)
+        return o, d, nd * na
+
+    @staticmethod
+    def _cast_args(n, times, group):
+        """cast_rays' motion times (a number or a sequence of 1 .. RTX_CAST_MAX_TIMES finite
+        numbers) as a float64 array, and ``group`` checked against the n rays."""
+        try:
+            ts = np.atleast_1d(np.asarray(times, np.float64))
+        except (TypeError, ValueError):
+            raise ValueError("times must be a number or a sequence of numbers") from None
+        if ts.ndim != 1 or not 1 <= ts.size <= N.RTX_CAST_MAX_TIMES:
+            raise ValueError("cast_rays takes 1 to %d motion times, got %s" % (N.RTX_CAST_MAX_TIMES, ts.shape))
+        with np.errstate(over="ignore"):
+            finite = np.isfinite(ts).all() and np.isfinite(ts.astype(np.float32)).all()
+        if not finite:
+            raise ValueError("motion times must be finite (as fp32)")
+        if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or group < 1:
+            raise ValueError("group must be an integer >= 1, got %r" % (group,))
+        if n % group:
+            raise ValueError("group %d does not divide the %d rays" % (group, n))
+        if int(group) * ts.size > 0x7FFFFFFF:
+            raise ValueError("group * len(times) must stay below 2^31")
+        return np.ascontiguousarray(ts), int(group)
+
+    def cast_rays_device(self, o, d, times=0.0, group=1, out=None, counters=None, stream=None):
+        """Scene.cast_ray (scene.py:81-116) for caller-built rays, batched (rtx_cast_rays):
+        ``o`` and ``d`` are contiguous float32 CUDA tensors [3, n] (origins, directions; the
+        directions are used as given, not normalised). Every ray is cast at every motion time
+        of ``times``; each run of ``group`` rays gives one colour, the fp32 mean of its
+        group * len(times) samples added in order (ray, then time) -- a pixel's loop nest.
+        Returns a float32 CUDA tensor [n / group, 3] (``out`` when given), which
+        fb_to_rgb8 takes. ``counters`` accumulate like render_device's. Uses nothing of the
+        camera and needs none. Asynchronous on ``stream`` (default: torch's current
+        stream); never synchronises."""
+        for name, a in (("o", o), ("d", d)):
+            if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[0] != 3 \
+                    or not a.is_contiguous():
+                raise ValueError("%s must be a contiguous float32 tensor of shape [3, n]" % name)
+        if o.shape != d.shape:
+            raise ValueError("o and d hold different numbers of rays: %d and %d" % (o.shape[1], d.shape[1]))
+        n = int(o.shape[1])
+        ts, group = self._cast_args(n, times, group)
+        shape = (n // group, 3)
+        if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape
+                                or out.dtype != torch.float32 or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of shape %s" % (shape,))
+        if counters is not None and (not isinstance(counters, torch.Tensor) or counters.numel() < N.RTX_COUNTERS
+                                     or counters.dtype != torch.int64):
+            raise ValueError("counters must be an int64 CUDA tensor with >= %d entries" % N.RTX_COUNTERS)
+        for name, a in (("o", o), ("d", d), ("out", out), ("counters", counters)):
+            if a is not None and (not a.is_cuda or a.device != o.device):
+                raise ValueError("%s must be a CUDA tensor on the rays' device" % name)
+        nat = self.native()
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=o.device)
+        st = stream if stream is not None else torch.cuda.current_stream()
+        vp = C.c_void_p
+        N.call("rtx_cast_rays", nat.h, n, vp(o.data_ptr()), vp(d.data_ptr()), _ptr(ts, C.c_double), int(ts.size), group,
+               vp(out.data_ptr()), vp(counters.data_ptr() if counters is not None else 0), vp(st.cuda_stream))
+        return out
+
+    def cast_rays(self, origins, directions, times=0.0, group=1):
+        """cast_rays_device for numpy rays [n, 3] (like intersect): returns the colours as a
+        numpy float32 array [n / group, 3]."""
+        o = np.asarray(origins, np.float32)
+        d = np.asarray(directions, np.float32)
+        for name, a in (("origins", o), ("directions", d)):
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("%s must have shape [n, 3], not %s" % (name, a.shape))
+        if o.shape != d.shape:
+            raise ValueError("origins and directions hold different numbers of rays: %d and %d"
+                             % (o.shape[0], d.shape[0]))
+        self._cast_args(o.shape[0], times, group)
+        od = torch.as_tensor(np.ascontiguousarray(o.T)).cuda()
+        dd = torch.as_tensor(np.ascontiguousarray(d.T)).cuda()
+        return self.cast_rays_device(od, dd, times, group).cpu().numpy()
 
     @property
     def samples_per_pixel(self):
