@@ -270,6 +270,49 @@ int rtx_render_aov(rtx_scene* scene, int32_t row0, int32_t nrows, int32_t frame,
                    float* position_dev, float* albedo_dev, int32_t* object_dev, int32_t* material_dev,
                    void* hip_stream);
 
+/* Occlusion buffers of rows [row0, row0 + nrows) of the strip (no reference counterpart): the
+ * visibility the reference computes per shadow ray and multiplies away (provided/scene.py:
+ * 148-167), kept, plus ambient occlusion. The ray, the first hit and the motion time t are
+ * rtx_render_aov's (DOF origin 0, AA origin 0, that sample's jitter draw, the first motion
+ * time of window `frame`); p and n below are the `position` and `normal` it writes. Buffers
+ * are pixel-major with row 0 at the top; each may be NULL (not written), but not both:
+ *   lights  u32 [nrows][ncols]  bit i set iff light i's shadow ray from p is NOT occluded at
+ *                               time t (scene.py:150-167, skip == False): a point light's has
+ *                               origin p, direction light.vector - p (one fp32 subtraction per
+ *                               component) and t_max 1.0, a directional light's origin p,
+ *                               direction -light.vector and t_max +inf. Pure visibility: the
+ *                               bit does not look at which way n faces. What rtx_occluded
+ *                               answers for that ray. 0 on a miss. A scene with more than 32
+ *                               lights gets RTX_ERR_INVALID when this buffer is requested.
+ *   ao      f32 [nrows][ncols]  fl32(u) / fl32(n_dirs), u the number of the n_dirs rays that
+ *                               rtx_occluded reports free; 1.0 on a miss. Ray k starts at p
+ *                               (no offset, like the reference's shadow rays; the epsilons of
+ *                               shadow_intersect apply), is cast at time t with t_max
+ *                               ao_radius, and runs along d_k below.
+ * ao_dirs is a host array of n_dirs local directions [n_dirs][3] (x, y, z), 1 <= n_dirs <=
+ * RTX_AO_MAX_DIRS, all finite, z along the normal; it is read during the call and passed to the
+ * kernel by value. They are used as given (not normalised; a z < 0 points below the surface).
+ * The frame is built in unfused fp32 in exactly this order:
+ *   n^ = normalize(n)            (glm normalize: n * (1 / sqrt(dot(n, n))))
+ *   s = copysignf(1, n^.z);  a = -1 / (s + n^.z);  b = (n^.x * n^.y) * a
+ *   T = (1 + ((s * n^.x) * n^.x) * a,  s * b,  -(s * n^.x))
+ *   U = (b,  s + ((n^.y * n^.y) * a),  -n^.y)
+ *   d_k = ((x_k * T) + (y_k * U)) + (z_k * n^)      per component
+ * The hemisphere is about the STORED normal: it is not flipped toward the viewer, so a surface
+ * seen from behind (the inside of a sphere, a plane from below) sends its rays away from the
+ * camera's side. A hit whose normal has zero length is outside the contract. ao_radius is
+ * > 0 or +inf. ao_dirs, n_dirs and ao_radius are ignored when ao_dev is NULL.
+ * Both answers are bit-identical to the reference's shadow_intersect loop for those rays.
+ * Asynchronous on the stream; the stream-ordering and graph-capture rules are rtx_render_aov's.
+ * RTX_ERR_STATE before rtx_camera_set; RTX_ERR_INVALID for a null scene, a row range outside
+ * the image, two null buffers, a frame outside the camera's sequence, `lights` on a scene with
+ * more than 32 lights, and with ao_dev: null ao_dirs, n_dirs outside [1, RTX_AO_MAX_DIRS], a
+ * non-finite direction component, an ao_radius that is NaN or <= 0. The arguments are checked
+ * before any HIP call. rtx_last_kernel is left as it is. */
+#define RTX_AO_MAX_DIRS 64
+int rtx_render_occlusion(rtx_scene* scene, int32_t row0, int32_t nrows, int32_t frame, uint32_t* lights_dev,
+                         float* ao_dev, const float* ao_dirs, int32_t n_dirs, double ao_radius, void* hip_stream);
+
 /* Rows rtx_render_groups writes for an image of `height` rows (-1: bad arguments). */
 int32_t rtx_group_rows(int32_t height, int32_t phase, int32_t stride);
 

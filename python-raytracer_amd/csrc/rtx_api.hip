@@ -12,6 +12,8 @@
 //   k_occluded    shadow any-hit of SoA rays (Geometry.shadow_intersect, scene.py:160-164)
 //   k_cast_rays   one work-item per sample of caller-built SoA rays: cast_ray's colour, the
 //                 samples of an output added in order (Scene.cast_ray, scene.py:81-116)
+//   k_occlusion   one work-item per output pixel: which lights reach the first sample's hit
+//                 (scene.py:150-167) and the share of free ambient-occlusion rays from it
 //   k_to_rgb8     (v * 255.0) truncated to uint8 (main.py:33)
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -4084,6 +4086,9 @@ namespace rtx {
 // loads; rtx_cast_rays finds them null there and reports RTX_ERR_UNSUPPORTED.
 __attribute__((weak)) hipError_t launch_cast_ext_m0(int, unsigned, size_t, hipStream_t, const SceneView&, const CastLaunch&);
 __attribute__((weak)) hipError_t launch_cast_ext_m1(int, unsigned, size_t, hipStream_t, const SceneView&, const CastLaunch&);
+// (k_occlusion's, likewise: rtx_render_occlusion reports RTX_ERR_UNSUPPORTED without them)
+__attribute__((weak)) hipError_t launch_occlusion_ext_m0(bool, unsigned, size_t, hipStream_t, const KParams*, const OccLaunch&);
+__attribute__((weak)) hipError_t launch_occlusion_ext_m1(bool, unsigned, size_t, hipStream_t, const KParams*, const OccLaunch&);
 }  // namespace rtx
 
 extern "C" {
@@ -4139,6 +4144,65 @@ int rtx_cast_rays(rtx_scene* s, int64_t n, const float* ro, const float* rd, con
     else { if (s->has_secondary) RTX_CAST_C(false, true); else RTX_CAST_C(false, false); }
 #undef RTX_CAST_C
 #undef RTX_CAST
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_render_occlusion(rtx_scene* s, int32_t row0, int32_t nrows, int32_t frame, uint32_t* lights_dev, float* ao_dev,
+                         const float* ao_dirs, int32_t n_dirs, double ao_radius, void* stream) {
+    if (!s) return fail(RTX_ERR_INVALID, "rtx_render_occlusion: null scene");
+    if (!s->cam_set) return fail(RTX_ERR_STATE, "rtx_render_occlusion: rtx_camera_set was not called");
+    if (row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > s->kp.height)
+        return fail(RTX_ERR_INVALID, "rtx_render_occlusion: row range outside the image");
+    if (!lights_dev && !ao_dev)
+        return fail(RTX_ERR_INVALID, "rtx_render_occlusion: no buffer requested (both pointers are null)");
+    // an ordinary camera holds one window (n_frames 0): frame 0
+    if (frame < 0 || frame >= std::max(s->kp.n_frames, 1))
+        return fail(RTX_ERR_INVALID, "rtx_render_occlusion: frame " + std::to_string(frame) + " outside the camera's " +
+                                         std::to_string(std::max(s->kp.n_frames, 1)) + " window(s)");
+    if (lights_dev && s->view.n_lights > 32)
+        return fail(RTX_ERR_INVALID, "rtx_render_occlusion: the light mask holds 32 lights, the scene has " +
+                                         std::to_string(s->view.n_lights));
+    OccLaunch L{lights_dev, ao_dev, row0, nrows, frame * s->kp.n_times, 0, INFINITY, {}};
+    if (ao_dev) {
+        if (!ao_dirs || n_dirs < 1 || n_dirs > RTX_AO_MAX_DIRS)
+            return fail(RTX_ERR_INVALID, "rtx_render_occlusion: 1 to " + std::to_string(RTX_AO_MAX_DIRS) +
+                                             " ambient-occlusion directions, got " +
+                                             (ao_dirs ? std::to_string(n_dirs) : std::string("a null array")));
+        for (int k = 0; k < 3 * n_dirs; ++k) {
+            if (!std::isfinite(ao_dirs[k]))
+                return fail(RTX_ERR_INVALID, "rtx_render_occlusion: direction " + std::to_string(k / 3) + " is not finite");
+            L.dirs[k / 3][k % 3] = ao_dirs[k];
+        }
+        if (!(ao_radius > 0.0))  // (NaN too)
+            return fail(RTX_ERR_INVALID, "rtx_render_occlusion: ao_radius must be > 0 or +inf");
+        L.n_dirs = n_dirs;
+        L.radius = ao_radius;
+    }
+    if (nrows == 0) return RTX_OK;
+    if (s->has_ext && !(s->has_mesh ? launch_occlusion_ext_m1 : launch_occlusion_ext_m0))
+        return fail(RTX_ERR_UNSUPPORTED, "rtx_render_occlusion: this build holds no hierarchy/texture kernels");
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != s->device)
+        return fail(RTX_ERR_STATE, "rtx_render_occlusion: the scene lives on device " + std::to_string(s->device) +
+                                       ", the current device is " + std::to_string(cur));
+    const int blk = s->has_ext ? kBlock<true> : kBlock<false>;
+    const int64_t nblocks = (launch_items(nrows, s->kp.ncols) + blk - 1) / blk;
+    if (nblocks > 0x7fffffff) return fail(RTX_ERR_INVALID, "rtx_render_occlusion: launch too large");
+    const KParams* kp = s->d_kp;
+    const bool jit = s->kp.jitter != RTX_JITTER_OFF;
+    hipStream_t st = (hipStream_t)stream;
+    if (s->has_ext) {  // precompiled in rtx_kern_ext_m{0,1}.hip
+        const size_t lds = (size_t)s->hlevels * 9 * sizeof(float) * kBlock<true>;
+        RTX_HIP(s->has_mesh ? launch_occlusion_ext_m1(jit, (unsigned)nblocks, lds, st, kp, L)
+                            : launch_occlusion_ext_m0(jit, (unsigned)nblocks, lds, st, kp, L));
+        return RTX_OK;
+    }
+#define RTX_OCCL(M, J) \
+    hipLaunchKernelGGL((k_occlusion<M, false, J>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0, st, kp, L)
+    if (s->has_mesh) { if (jit) RTX_OCCL(true, true); else RTX_OCCL(true, false); }
+    else { if (jit) RTX_OCCL(false, true); else RTX_OCCL(false, false); }
+#undef RTX_OCCL
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

@@ -60,4 +60,12 @@ hipError_t launch_cast_ext_m1(int sel, unsigned nblocks, size_t lds_bytes, hipSt
     return hipGetLastError();
 }
 
+hipError_t launch_occlusion_ext_m1(bool jitter, unsigned nblocks, size_t lds_bytes, hipStream_t stream, const KParams* kp,
+                                   const OccLaunch& L) {
+    constexpr int B = kBlock<true>;
+    if (jitter) hipLaunchKernelGGL((k_occlusion<true, true, true>), dim3(nblocks), dim3(B), lds_bytes, stream, kp, L);
+    else hipLaunchKernelGGL((k_occlusion<true, true, false>), dim3(nblocks), dim3(B), lds_bytes, stream, kp, L);
+    return hipGetLastError();
+}
+
 }  // namespace rtx

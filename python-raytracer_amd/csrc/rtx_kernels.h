@@ -1003,6 +1003,90 @@ __global__ __launch_bounds__(kBlock<X>) void k_aov(const KParams* __restrict__ P
     }
 }
 
+// The per-call block of the occlusion pass (rtx_render_occlusion): rows [row0, row0 + nrows)
+// of the strip, the frame's first motion time P.times[tbase], one pointer per buffer
+// ([nrows][ncols]; null: not wanted) and the ambient-occlusion rays by value: n_dirs local
+// directions (x, y along the tangents, z along the normal) and their t_max.
+struct OccLaunch {
+    uint32_t* lights;
+    float* ao;
+    int32_t row0, nrows, tbase, n_dirs;
+    double radius;
+    float dirs[RTX_AO_MAX_DIRS][3];
+};
+
+// Visibility at the first hit of each pixel (no reference counterpart). The ray, the hit and
+// the motion time are k_aov's, statement for statement, and so is the mapping: one lane per
+// pixel, an 8x8 tile per wave, ragged edge lanes inactive, the tile's primary bin, no
+// pixel-in-tile. From the hit's position p and normal n (the values k_aov stores):
+//   lights  bit li = light li's shadow ray from p is free (scene.py:150-167, skip == False).
+//           The tests are regular_lighting's level-0 calls of occluded, argument for argument
+//           (the light's index, the hit's flat object, the tile's shadow-bin word), so they use
+//           what a render's use: light grids, shadow bins, plane self tests, directional
+//           shadow grids -- all built for the camera's own hit points, which p is.
+//   ao      the share of n_dirs rays from p that are free up to t_max = radius; ray k runs
+//           along x_k T + y_k U + z_k n^ in the branchless orthonormal frame of n^ =
+//           normalize(n) (unfused fp32 in the order written below). These are not camera or
+//           light rays: they go through occluded with its defaults (light -1, self_obj -1,
+//           every object), which reads none of the camera's or the lights' tables.
+// A miss stores 0 and 1.0. Lanes that missed sit out both loops (as in cast_ray, which
+// leaves before regular_lighting): occluded's wave votes count active lanes only.
+template <bool MESH, bool X, bool JIT>
+__global__ __launch_bounds__(kBlock<X>) void k_occlusion(const KParams* __restrict__ Pp, const OccLaunch L) {
+    constexpr int B = kBlock<X>;
+    extern __shared__ float hstack[];  // X: [level][9][thread] (dynamic size)
+    const HStack hs{hstack + threadIdx.x, B};
+    const KParams& P = *Pp;
+    const int32_t ncols = P.ncols;
+    const PixelRC px = pixel_rc<B>(ncols, 0);
+    if (!(px.r < L.nrows && px.c < ncols)) return;
+    const int32_t bin = RTX_TILE == 1 ? primary_bin(P.S, L.row0 + (px.r & ~7), px.c & ~7) : -1;
+    const int j = P.height - 1 - (L.row0 + px.r);  // reference row index (y grows upward)
+    const f3 o = sample_origin<JIT>(P, px.c, j, 0, 0);
+    const f3 d = normalize(sub(pixel_focal(P, px.c, j), ld3(P.dof_o)));  // scene.py:58
+    const float time = P.times[L.tbase];
+    Tally tl = {};
+    HHit hh;
+    const Hit h = closest_hit<MESH, X, false>(P.S, o, d, time, tl, hs, hh, bin, nullptr, -1);
+    const bool hit = h.obj != -1;
+    uint32_t lit = 0u;
+    float open = 1.0f;
+    if (hit) {
+        const Surface sf = resolve_hit<MESH, X>(P.S, h, hh, o, d, time);
+        if (L.lights != nullptr) {
+            cptr<uint32_t> sbm = nullptr;  // the tile's shadow bins (regular_lighting's)
+            if (RTX_SHADOW_BINS && bin >= 0 && P.S.bin_shadow != nullptr)  // (wave-uniform)
+                sbm = P.S.bin_shadow + (int64_t)wave_uniform(bin) * P.S.n_lights;
+            for (int li = 0; li < P.S.n_lights; ++li) {
+                const DLight Lt = P.S.lights[li];
+                const bool point = Lt.type == LIGHT_POINT;
+                const f3 sdir = point ? sub(ld3(Lt.vec), sf.position) : ld3(Lt.negvec);
+                const double t_max = point ? 1.0 : (double)INFINITY;
+                if (!occluded<MESH, X, false>(P.S, sf.position, sdir, t_max, time, tl, hs, nullptr, li, h.obj,
+                                              sbm ? sbm[li] : ~0u))
+                    lit |= 1u << li;
+            }
+        }
+        if (L.ao != nullptr) {
+            const f3 n = normalize(sf.normal);
+            const float s = __builtin_copysignf(1.0f, n.z);
+            const float a = -1.0f / (s + n.z);
+            const float b = (n.x * n.y) * a;
+            const f3 T = mk(1.0f + ((s * n.x) * n.x) * a, s * b, -(s * n.x));
+            const f3 U = mk(b, s + ((n.y * n.y) * a), -n.y);
+            int32_t free_rays = 0;
+            for (int k = 0; k < L.n_dirs; ++k) {
+                const f3 dk = add(add(scale(T, L.dirs[k][0]), scale(U, L.dirs[k][1])), scale(n, L.dirs[k][2]));
+                if (!occluded<MESH, X, false>(P.S, sf.position, dk, L.radius, time, tl, hs)) ++free_rays;
+            }
+            open = (float)free_rays / (float)L.n_dirs;
+        }
+    }
+    const int64_t p = (int64_t)px.r * ncols + px.c;
+    if (L.lights != nullptr) L.lights[p] = lit;
+    if (L.ao != nullptr) L.ao[p] = open;
+}
+
 // The per-call block of rtx_cast_rays: n caller-built rays as SoA fp32 [3][n] (rtx_intersect's
 // layout), the motion times by value, and the output, fp32 [n / group][3].
 struct CastLaunch {

@@ -35,4 +35,12 @@ hipError_t launch_cast_ext_m0(int sel, unsigned nblocks, size_t lds_bytes, hipSt
                               const CastLaunch& L);
 hipError_t launch_cast_ext_m1(int sel, unsigned nblocks, size_t lds_bytes, hipStream_t stream, const SceneView& S,
                               const CastLaunch& L);
+
+// k_occlusion (rtx_render_occlusion) of the hierarchy/texture variants: nblocks one-wave blocks
+// with lds_bytes of dynamic LDS; jitter: the camera's JITTER variant.
+struct OccLaunch;
+hipError_t launch_occlusion_ext_m0(bool jitter, unsigned nblocks, size_t lds_bytes, hipStream_t stream, const KParams* kp,
+                                   const OccLaunch& L);
+hipError_t launch_occlusion_ext_m1(bool jitter, unsigned nblocks, size_t lds_bytes, hipStream_t stream, const KParams* kp,
+                                   const OccLaunch& L);
 }  // namespace rtx

@@ -27,6 +27,13 @@ counterpart; default: all six) as (H, W) or (H, W, 3) arrays of one .npz file.
 An equirectangular W x H panorama about the scene's camera position (no reference
 counterpart: rtx.panorama_rays shaded by Scene.cast_rays_device at the camera's motion times),
 in place of the camera's image.
+
+    python -m rtx.main --infile S.json --outfile out.png --occlusion occ.npz [--ao-samples K] [--ao-radius R]
+
+Besides the image, the occlusion buffers of Scene.render_occlusion (no reference counterpart)
+as (H, W) arrays of one .npz file: `lights` (uint32, bit i: light i reaches the pixel's first
+hit) and `ao` (float32, the share of K ambient-occlusion rays of length R that are free;
+default 16 rays, unbounded).
 """
 import argparse
 import json
@@ -34,6 +41,7 @@ import os
 
 import numpy
 
+from ._native import RTX_AO_MAX_DIRS
 from .scene import AOV_NAMES
 
 
@@ -58,7 +66,25 @@ def parse(argv=None):
                    help="the buffers to write (default: depth normal position albedo object material)")
     p.add_argument("--panorama", type=int, nargs=2, default=None, metavar=("W", "H"),
                    help="write an equirectangular W x H panorama about the camera position instead of its image")
+    p.add_argument("--occlusion", type=str, default=None, metavar="FILE.npz",
+                   help="also write the occlusion buffers (Scene.render_occlusion: lights, ao) to this .npz file")
+    p.add_argument("--ao-samples", type=int, default=None, metavar="K",
+                   help="ambient-occlusion rays per pixel, 1 .. 64 (default 16)")
+    p.add_argument("--ao-radius", type=float, default=None, metavar="R",
+                   help="length of the ambient-occlusion rays, > 0 (default: unbounded)")
     args = p.parse_args(argv)
+    if args.occlusion is not None:
+        if args.distributed:
+            p.error("--occlusion renders on one GPU: it cannot be combined with --distributed")
+        if args.frames is not None or args.panorama is not None:
+            p.error("--occlusion writes the buffers of the camera's one frame: it cannot be combined with "
+                    "--frames or --panorama")
+        if args.ao_samples is not None and not 1 <= args.ao_samples <= RTX_AO_MAX_DIRS:
+            p.error("--ao-samples takes 1 .. %d" % RTX_AO_MAX_DIRS)
+        if args.ao_radius is not None and not args.ao_radius > 0.0:
+            p.error("--ao-radius must be > 0")
+    elif args.ao_samples is not None or args.ao_radius is not None:
+        p.error("--ao-samples and --ao-radius need --occlusion")
     if args.panorama is not None:
         if args.distributed or args.frames is not None or args.aovs is not None or args.subimage is not None \
                 or args.tasks is not None:
@@ -138,6 +164,23 @@ def write_aovs(sc, args):
     return args.aovs
 
 
+def write_occlusion(sc, args):
+    """The occlusion buffers of the frame (or strip) as one .npz file: `lights` uint32 and `ao`
+    float32, (H, W) arrays, row 0 at the top."""
+    kw = {}
+    if args.subimage is not None and args.tasks is not None:
+        kw = dict(subimage=args.subimage, tasks=args.tasks)
+    if args.ao_samples is not None:
+        kw["ao_samples"] = args.ao_samples
+    if args.ao_radius is not None:
+        kw["ao_radius"] = args.ao_radius
+    b = sc.render_occlusion(("lights", "ao"), **kw)
+    with open(args.occlusion, "wb") as f:  # (numpy.savez would append ".npz" to a bare name)
+        # (the device tensor is int32 holding the mask's bits: torch has no CUDA uint32 arithmetic)
+        numpy.savez(f, lights=b["lights"].cpu().numpy().view(numpy.uint32), ao=b["ao"].cpu().numpy())
+    return args.occlusion
+
+
 def render_panorama(sc, width, height):
     """The panorama's PNG bytes, uint8 (height, width, 3): panorama_rays shaded at the camera's
     motion times, converted on the device like a render (rtx_fb_to_rgb8)."""
@@ -197,6 +240,8 @@ def main(argv=None):
         Image.fromarray(rgb).save(args.outfile)
     if args.aovs is not None:
         write_aovs(full_scene, args)
+    if args.occlusion is not None:
+        write_occlusion(full_scene, args)
 
 
 if __name__ == "__main__":

@@ -27,6 +27,8 @@ DEFAULT_SEED = 0x5EED
 AOV_NAMES = ("depth", "normal", "position", "albedo", "object", "material")
 _AOV_VEC = ("normal", "position", "albedo")
 _AOV_INT = ("object", "material")
+# the occlusion buffers of Scene.render_occlusion (rtx_render_occlusion)
+OCCLUSION_NAMES = ("lights", "ao")
 
 
 def _ptr(a, ctype):
@@ -139,6 +141,24 @@ def panorama_rays(vc, width, height):
     d = np.sin(theta) * (np.cos(phi) * -w + np.sin(phi) * u) + np.cos(theta) * v
     o = np.broadcast_to(np.asarray(vc.position, np.float32).reshape(3), d.shape)
     return np.ascontiguousarray(o).reshape(-1, 3), d.astype(np.float32).reshape(-1, 3)
+
+
+def cosine_directions(k):
+    """The default ambient-occlusion directions of Scene.render_occlusion: ``k`` cosine-weighted
+    directions about +z (Malley's method), float32 [k, 3]. (x, y) are the sunflower points of
+    the unit disk (Scene._sunflower_spread's radii and angles, scene.py:118-138) in fp64,
+    z = sqrt(max(0, 1 - x^2 - y^2)); the three are rounded to fp32 once. The outermost point
+    lies on the disk's rim, so the last direction runs along the surface (z is 0 or a rounding
+    residue)."""
+    from .helperclasses import _sunflower_terms
+    k = int(k)
+    if k < 1:
+        raise ValueError("cosine_directions needs k >= 1")
+    sq, co, si, sn = _sunflower_terms(k)
+    r = sq / sn
+    x, y = r * co, r * si
+    z = np.sqrt(np.maximum(0.0, 1.0 - x * x - y * y))
+    return np.stack([x, y, z], axis=1).astype(np.float32)
 
 
 _GENERATION = itertools.count(1)
@@ -546,6 +566,96 @@ class Scene:
         oi, mi = int(b["object"]), int(b["material"])
         return dict(object=self.objects[oi] if oi >= 0 else None, material=self.materials[mi] if mi >= 0 else None,
                     depth=float(b["depth"]), position=b["position"], normal=b["normal"], albedo=b["albedo"])
+
+    # ------------------------------------------------------------------ occlusion buffers
+    def render_occlusion(self, buffers=OCCLUSION_NAMES, ao_samples=16, ao_radius=math.inf, ao_dirs=None, subimage=0,
+                         tasks=1, row0=0, nrows=None, windows=None, frame=0, out=None, stream=None):
+        """Visibility at the first hit of each pixel (rtx_render_occlusion; no reference
+        counterpart): a dict name -> CUDA tensor [nrows, W] for the chosen ``buffers`` of image
+        rows [row0, row0 + nrows) (row 0 = top) of the strip. The ray, the hit and the motion
+        time are render_aovs' (``windows`` / ``frame`` as there); p and n are its "position" and
+        "normal".
+
+        "lights": bit i is set iff light i's shadow ray from p is free (scene.py:150-167) --
+        what ``occluded`` answers for it; 0 on a miss. At most 32 lights. torch has no CUDA
+        uint32 arithmetic, so the mask is handed out as **int32** holding the same bits (bit
+        31 is the sign; ``.cpu().numpy().view(numpy.uint32)`` gives the unsigned words).
+
+        "ao": float32, the share of the ambient-occlusion rays from p that are free up to
+        ``ao_radius`` (> 0 or inf); 1.0 on a miss. The rays run along ``ao_dirs``, float32
+        [K, 3] local directions with z along the normal (1 <= K <= 64, finite; default:
+        ``cosine_directions(ao_samples)``), in the orthonormal frame rtx.h spells out. The
+        hemisphere is about the stored normal, which is not flipped toward the viewer.
+
+        ``out``: a dict of preallocated contiguous CUDA tensors for some or all of the names.
+        Asynchronous on ``stream`` (default: torch's current stream)."""
+        names = [buffers] if isinstance(buffers, str) else list(buffers)
+        if not names:
+            raise ValueError("render_occlusion needs at least one of %s" % (OCCLUSION_NAMES,))
+        for n in names:
+            if n not in OCCLUSION_NAMES:
+                raise ValueError("unknown occlusion buffer %r (known: %s)" % (n, ", ".join(OCCLUSION_NAMES)))
+        if len(set(names)) != len(names):
+            raise ValueError("an occlusion buffer is named twice: %s" % (names,))
+        if windows is not None:
+            windows = sequence_windows(windows)
+        frame = int(frame)
+        if not 0 <= frame < (1 if windows is None else len(windows)):
+            raise ValueError("frame %d outside the %d window(s)" % (frame, 1 if windows is None else len(windows)))
+        H, W = self.vc.height, strip_columns(self.vc.width, subimage, tasks)[1]
+        row0 = int(row0)
+        nrows = H - row0 if nrows is None else int(nrows)
+        if row0 < 0 or nrows < 0 or row0 + nrows > H:
+            raise ValueError("rows [%d, %d) outside the image of %d rows" % (row0, row0 + nrows, H))
+        if "lights" in names and len(self.lights) > 32:
+            raise ValueError("the light mask holds 32 lights, the scene has %d" % len(self.lights))
+        dirs, radius = None, math.inf
+        if "ao" in names:
+            if ao_dirs is None:
+                if isinstance(ao_samples, bool) or not isinstance(ao_samples, (int, np.integer)) \
+                        or not 1 <= ao_samples <= N.RTX_AO_MAX_DIRS:
+                    raise ValueError("ao_samples must be an integer in [1, %d], got %r" % (N.RTX_AO_MAX_DIRS, ao_samples))
+                dirs = cosine_directions(int(ao_samples))
+            else:
+                try:
+                    with np.errstate(over="ignore"):
+                        dirs = np.ascontiguousarray(np.asarray(ao_dirs, np.float64).astype(np.float32))
+                except (TypeError, ValueError):
+                    raise ValueError("ao_dirs must be an array of shape [K, 3]") from None
+                if dirs.ndim != 2 or dirs.shape[1] != 3 or not 1 <= dirs.shape[0] <= N.RTX_AO_MAX_DIRS:
+                    raise ValueError("ao_dirs must have shape [K, 3] with 1 <= K <= %d, not %s"
+                                     % (N.RTX_AO_MAX_DIRS, dirs.shape))
+                if not np.isfinite(dirs).all():
+                    raise ValueError("ao_dirs must be finite (as fp32)")
+            try:
+                radius = float(ao_radius)
+            except (TypeError, ValueError):
+                raise ValueError("ao_radius must be a number") from None
+            if not radius > 0.0:  # (NaN too)
+                raise ValueError("ao_radius must be > 0 or inf, got %r" % (ao_radius,))
+        out = {} if out is None else dict(out)
+        for n in out:
+            if n not in names:
+                raise ValueError("out holds %r, which is not among the requested buffers %s" % (n, names))
+        dtypes = dict(lights=torch.int32, ao=torch.float32)
+        for n in names:
+            t = out.get(n)
+            if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (nrows, W) or t.dtype != dtypes[n]
+                                  or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("out[%r] must be a contiguous %s CUDA tensor of shape %s"
+                                 % (n, str(dtypes[n]).replace("torch.", ""), (nrows, W)))
+        self._set_camera(subimage, tasks, windows)
+        for n in names:
+            if out.get(n) is None:
+                out[n] = torch.empty((nrows, W), dtype=dtypes[n], device="cuda")
+        st = stream if stream is not None else torch.cuda.current_stream()
+        if nrows > 0:  # (the tensors of an empty block have no storage to point at)
+            vp = C.c_void_p
+            N.call("rtx_render_occlusion", self._native.h, row0, nrows, frame,
+                   vp(out["lights"].data_ptr() if "lights" in out else 0), vp(out["ao"].data_ptr() if "ao" in out else 0),
+                   _ptr(dirs, C.c_float) if dirs is not None else None, 0 if dirs is None else int(dirs.shape[0]),
+                   radius, vp(st.cuda_stream))
+        return {n: out[n] for n in names}
 
     def render(self, subimage: int = 0, tasks: int = 1) -> np.ndarray:
         """scene.py:35-79 — returns float64 (strip_width, height, 3), [column, row-from-bottom]."""
