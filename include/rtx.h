@@ -382,7 +382,7 @@ int32_t rtx_jit_modules(void);
 
 /* Library options (no reference counterpart; INTEGRATION.md "Options"): process-wide
  * switches of the culling structures, the split hierarchy passes, the scene-specialized
- * kernels and their caches, by name ("split", "bins", "jit", ...). Each starts from
+ * kernels and their caches, by name ("split", "bins", "jit", "uniform_hit", ...). Each starts from
  * $RTX_<NAME> when that is set in the environment, else from its default; set them before
  * rendering (they are read per render / per camera upload, not synchronised with renders
  * on other threads). Values are text: a number, or a string for "jit_cache" / "jit_flags".

@@ -81,7 +81,7 @@ enum Opt {
     OPT_SELF_SKIP, OPT_TILE_SCHED, OPT_XCD_MAP, OPT_TILE_BLOCK, OPT_PRIM_ORIGIN, OPT_SPP, OPT_SPP_MIN, OPT_JIT, OPT_JIT_BAKE, OPT_JIT_EXT,
     OPT_JIT_DUMP, OPT_JIT_IDLE_BAKED, OPT_JIT_DISK_BAKED, OPT_JIT_CACHE, OPT_JIT_FLAGS, OPT_JIT_ILP, OPT_JIT_ASYNC,
     OPT_DEV_BINS, OPT_CHUNK_MODE, OPT_BIN_LDS, OPT_JIT_CSG, OPT_CSG_RAYS, OPT_CSG_SHADE, OPT_SETUP_LOG, OPT_SHADOW_BINS,
-    OPT_COUNT
+    OPT_UNIFORM_HIT, OPT_COUNT
 };
 struct OptDef {
     const char* name;
@@ -123,6 +123,7 @@ constexpr OptDef kOpts[OPT_COUNT] = {
     {"csg_shade", 0, false},                  // the shade pass compiled with them (measured no faster)
     {"setup_log", 0, false},                  // print the host time of each rtx_camera_set step
     {"shadow_bins", 1, false},                // per-bin occluder masks of level-0 shadow rays (2: scenes with secondary rays too)
+    {"uniform_hit", 1, false},                // wave-uniform hits shaded from literal records (scenes of few objects, no secondary rays)
 };
 struct OptVal {
     double v;
@@ -2267,6 +2268,15 @@ bool jit_spec(const std::string& arch, const SceneView& v, const KParams& kp, co
         opts.push_back("-mllvm");
         opts.push_back("-amdgpu-kernarg-preload-count=16");
     }
+    // wave-uniform hits shaded by a copy of the shading code per object (rtx_trace.h
+    // cast_ray; option uniform_hit): one-sample kernels with baked records of scenes of
+    // primary and shadow rays with at most kUniformHitMax objects. TwoSpheresPlane 1080p
+    // 19.85 -> 17.84 us, TorusMesh (the plane's copy; mesh hits stay per lane) 45.1 -> 43.7 us
+    // (DESIGN.md 8.U). Kernels with secondary rays keep cast_ray's loop as it is.
+    const int n_obj = v.n_plane + v.n_sphere + v.n_box + v.n_mesh;
+    if (!ext && !sec && !spp && kp.n_dof * kp.n_aa * kp.n_times == 1 && jit_bake_enabled() && !baked.empty() &&
+        n_obj <= kUniformHitMax && opt_on(OPT_UNIFORM_HIT))
+        opts.push_back("-DRTX_UNIFORM_HIT=" + std::to_string(n_obj));
     {  // option jit_flags (tools: cost probes, occupancy bounds); part of the cache key
         std::istringstream is(opt_str(OPT_JIT_FLAGS));
         for (std::string o; is >> o;) opts.push_back(o);

@@ -2853,7 +2853,10 @@ struct Surface {
     int32_t gobj;  // DObj whose get_diffuse shades the hit (textured or hierarchy Plane/AABB), or -1
 };
 
-template <bool MESH, bool X>
+// K >= 0: every live lane hit object K (cast_ray's wave-uniform dispatch), so the record
+// is read at a compile-time index -- literals in kernels with baked records -- and the
+// type branch below folds.
+template <bool MESH, bool X, int K = -1>
 RTX_HD Surface resolve_hit(const SceneView& S, const Hit& h, const HHit& hh, f3 o, f3 d, float time) {
     Surface sf;
     if (X && h.obj == kHierHit) {
@@ -2863,7 +2866,7 @@ RTX_HD Surface resolve_hit(const SceneView& S, const Hit& h, const HHit& hh, f3 
         sf.gobj = hh.gobj;
         return sf;
     }
-    const DObj ob = RTX_OBJ(S, h.obj);
+    const DObj ob = RTX_OBJ(S, K >= 0 ? K : h.obj);
     sf.gobj = (X && ob.has_tex) ? h.obj : -1;
     sf.position = add(o, scale(d, h.t32));  // getPoint(t): fl32(t64) == t32
     sf.mat = ob.mat0;
@@ -3072,6 +3075,56 @@ struct FrameStack {
     }
 };
 
+// Wave-uniform hits (RTX_UNIFORM_HIT = the scene's object count, defined by rtx_api.hip
+// jit_spec for one-sample kernels of primary and shadow rays with baked records; the host
+// emulation always has it). In almost every wave all lanes that hit anything hit one
+// object (99 % of TwoSpheresPlane's tiles at 1080p), yet each lane indexes the object
+// record, its type-dependent fields and the material with its own hit: three dependent
+// vector trips, a type dispatch and record fields held in VGPRs. cast_ray instead votes on
+// the hit object and, when the live lanes agree, switches on the scalar index to a copy of
+// the shading code compiled for object K (shade_uniform<K>): the record's fields are
+// literal operands, resolve_hit's type branch folds, self_obj and the plane_self index are
+// constants in the shadow tests, a sphere's material is a literal record and a checker
+// plane's a select between two (words on which both agree fold). Waves that see two
+// objects, and mesh hits, keep the per-lane path. The arithmetic is the same on the same
+// values, so every result is unchanged.
+// On the host the macro is a constant, whatever the option uniform_hit says: the tests' host
+// emulation shades every hit on one of a flat scene's first four objects by the copy, and
+// runs the per-lane path only for further objects, mesh hits, and scenes with secondary
+// rays, hierarchies or textures (the GPU tests compare both paths, option on and off).
+#if !defined(RTX_UNIFORM_HIT) && !defined(__HIP_DEVICE_COMPILE__)
+#define RTX_UNIFORM_HIT 4  // (host emulation: one lane per wave, every hit is uniform)
+#endif
+constexpr int kUniformHitMax = 4;  // objects with a shading copy of their own (code size)
+// One of two records, word by word, as a ^ ((a ^ b) & mask): with literal records a word on
+// which both agree folds to the literal and the others cost two bit operations. (Written
+// as `second ? b : a` the compiler merges the two literals back into one load at a per-lane
+// address, the trip this path exists to remove.)
+RTX_HD DMat select_mat(bool second, const DMat& a, const DMat& b) {
+    constexpr int kWords = 18;  // up to the record's tail padding
+    static_assert(__builtin_offsetof(DMat, hardness) + sizeof(double) == 4 * kWords, "DMat's fields are 18 words");
+    uint32_t wa[kWords], wb[kWords], wm[kWords];
+    __builtin_memcpy(wa, &a, sizeof(wa));
+    __builtin_memcpy(wb, &b, sizeof(wb));
+    const uint32_t mask = second ? ~0u : 0u;
+    for (int i = 0; i < kWords; ++i) wm[i] = wa[i] ^ ((wa[i] ^ wb[i]) & mask);
+    DMat m = a;
+    __builtin_memcpy(&m, wm, sizeof(wm));
+    return m;
+}
+// regular_lighting of a camera ray's hit h on flat object K (not a mesh), which every live
+// lane of the wave hit: cast_ray's resolve_hit, material and lighting with K for h.obj.
+template <bool MESH, bool COUNT, int K>
+RTX_HD f3 shade_uniform(const SceneView& S, const Hit& h, const HHit& hh, f3 o, f3 d, float time, Tally& tl,
+                        const HStack& hs, int32_t bin) {
+    const Surface sf = resolve_hit<MESH, false, K>(S, h, hh, o, d, time);
+    // Surface::mat is the object's first material, or one of a checker plane's two
+    const DObj ob = RTX_OBJ(S, K);
+    const DMat m0 = RTX_MAT(S, ob.mat0);
+    const DMat m = (ob.type != OBJ_PLANE || ob.nmat == 1) ? m0 : select_mat(sf.mat == ob.mat1, m0, RTX_MAT(S, ob.mat1));
+    return regular_lighting<MESH, false, COUNT>(S, d, sf.position, sf.normal, m, ld3(m.diffuse), time, tl, hs, -1, K, bin);
+}
+
 template <bool MESH, bool SEC, bool X, bool COUNT>
 RTX_HD f3 cast_ray(const SceneView& S, f3 o, f3 d, float time, Tally& tl, const FrameStack& fs, const HStack& hs,
                    int32_t bin = -1, const OriginTerms* prim = nullptr, int32_t blane = -1) {
@@ -3088,6 +3141,35 @@ RTX_HD f3 cast_ray(const SceneView& S, f3 o, f3 d, float time, Tally& tl, const 
         const Hit h = closest_hit<MESH, X, COUNT>(S, o, d, time, tl, hs, hh, level == 0 ? bin : -1,
                                                   level == 0 ? prim : nullptr, blane);
         if (h.obj == -1) break;  // miss -> black
+#ifdef RTX_UNIFORM_HIT
+        // (cost probes 2 and 7 end the per-lane path below before its lighting: probe builds
+        // keep that path for every wave)
+        if (!SEC && !X && !RTX_PROBE(2) && !RTX_PROBE(7)) {
+            // u is the hit of a live lane: the lanes that missed left through the break above.
+            // It only selects a case and never indexes anything: a value no case matches
+            // (-1 included) falls through to the per-lane path, so the switch has no default.
+            const int32_t u = wave_uniform(h.obj);
+            if (u < kUniformHitMax && u < RTX_UNIFORM_HIT && RTX_ALL(h.obj == u)) {
+                bool taken = false;
+#define RTX_UNIFORM_CASE(k)                                                                             \
+    case k:                                                                                             \
+        if (k < RTX_UNIFORM_HIT && RTX_OBJ(S, k).type != OBJ_MESH) {                                    \
+            tail = clamp01(shade_uniform<MESH, COUNT, k>(S, h, hh, o, d, time, tl, hs, bin));           \
+            taken = true;                                                                               \
+        }                                                                                               \
+        break;
+                switch (u) {
+                    RTX_UNIFORM_CASE(0)
+                    RTX_UNIFORM_CASE(1)
+                    RTX_UNIFORM_CASE(2)
+                    RTX_UNIFORM_CASE(3)
+                }
+#undef RTX_UNIFORM_CASE
+                static_assert(kUniformHitMax == 4, "one case per object with a shading copy");
+                if (taken) break;
+            }
+        }
+#endif
         const Surface sf = resolve_hit<MESH, X>(S, h, hh, o, d, time);
         const DMat m = RTX_MAT(S, sf.mat);
         f3 n = sf.normal;
