@@ -3471,34 +3471,69 @@ int sequence_range(const char* fn, const rtx_scene* s, int32_t frame0, int32_t n
     return RTX_OK;
 }
 
-int render_rows(const char* fn, rtx_scene* s, int32_t row0, int32_t nrows, void* out_dev, uint64_t* counters_dev,
-                void* stream, bool out8, int32_t nframes = 1, int64_t fstride = 0, int32_t frame0 = -1) {
+// The argument checks the entry points share; fn, the public function's name, leads every message.
+int check_camera(const char* fn, const rtx_scene* s) {
     if (!s) return fail(RTX_ERR_INVALID, std::string(fn) + ": null scene");
     if (!s->cam_set) return fail(RTX_ERR_STATE, std::string(fn) + ": rtx_camera_set was not called");
-    if (row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > s->kp.height)
-        return fail(RTX_ERR_INVALID, std::string(fn) + ": row range outside the image");
-    const int64_t block_bytes = (int64_t)nrows * s->kp.ncols * 3 * (out8 ? 1 : 4);
-    if (nframes < 1 || nframes > 65535 || (nframes > 1 && fstride < block_bytes) || (!out8 && fstride % 4))
-        return fail(RTX_ERR_INVALID, std::string(fn) + ": need 1 <= nframes <= 65535 and frames that do not overlap");
-    Launch L;
-    if (int rc = sequence_range(fn, s, frame0, nframes, L)) return rc;
-    if (nrows == 0) return RTX_OK;
-    if (!out_dev) return fail(RTX_ERR_INVALID, std::string(fn) + ": null framebuffer");
-    L.fb = static_cast<float*>(out_dev);
-    L.row0 = row0;
-    L.nrows = nrows;
-    L.gphase = 0;
-    L.gstride = 0;
-    L.fstride = nframes > 1 ? fstride : 0;
-    return render_launch(s, L, counters_dev, stream, out8, nframes);
+    return RTX_OK;
 }
 
-int render_groups(const char* fn, rtx_scene* s, int32_t phase, int32_t stride, void* out_dev, uint64_t* counters_dev,
-                  void* stream, bool out8, int32_t nframes = 1, int64_t fstride = 0, int32_t frame0 = -1) {
-    if (!s) return fail(RTX_ERR_INVALID, std::string(fn) + ": null scene");
-    if (!s->cam_set) return fail(RTX_ERR_STATE, std::string(fn) + ": rtx_camera_set was not called");
-    const int32_t nrows = rtx_group_rows(s->kp.height, phase, stride);
-    if (nrows < 0) return fail(RTX_ERR_INVALID, std::string(fn) + ": need 0 <= phase < stride");
+int check_rows(const char* fn, const rtx_scene* s, int32_t row0, int32_t nrows) {
+    if (row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > s->kp.height)
+        return fail(RTX_ERR_INVALID, std::string(fn) + ": row range outside the image");
+    return RTX_OK;
+}
+
+// (an ordinary camera holds one window, n_frames 0: frame 0)
+int check_frame(const char* fn, const rtx_scene* s, int32_t frame) {
+    if (frame < 0 || frame >= std::max(s->kp.n_frames, 1))
+        return fail(RTX_ERR_INVALID, std::string(fn) + ": frame " + std::to_string(frame) + " outside the camera's " +
+                                         std::to_string(std::max(s->kp.n_frames, 1)) + " window(s)");
+    return RTX_OK;
+}
+
+int check_device(const char* fn, const rtx_scene* s) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != s->device)
+        return fail(RTX_ERR_STATE, std::string(fn) + ": the scene lives on device " + std::to_string(s->device) +
+                                       ", the current device is " + std::to_string(cur));
+    return RTX_OK;
+}
+
+int check_grid(const char* fn, int64_t nblocks) {
+    if (nblocks > 0x7fffffff) return fail(RTX_ERR_INVALID, std::string(fn) + ": launch too large");
+    return RTX_OK;
+}
+
+// The blocks of a tile-mapped launch over nrows rows of the strip: one lane per pixel.
+int tile_blocks(const char* fn, const rtx_scene* s, int32_t nrows, int64_t& nblocks) {
+    const int blk = s->has_ext ? kBlock<true> : kBlock<false>;
+    nblocks = (launch_items(nrows, s->kp.ncols) + blk - 1) / blk;
+    return check_grid(fn, nblocks);
+}
+
+// The dynamic LDS of a hierarchy/texture kernel's block: its threads' stacks, [level][9][thread].
+size_t hstack_bytes(const rtx_scene* s, int block) { return (size_t)s->hlevels * 9 * sizeof(float) * block; }
+
+// The rows of a render: [row0, row0 + nrows) of the strip, or (stride > 0) its interleaved 8-row
+// groups phase, phase + stride, ...
+struct RowSel {
+    int32_t row0, nrows, phase, stride;
+    bool groups;
+};
+RowSel strip_rows(int32_t row0, int32_t nrows) { return RowSel{row0, nrows, 0, 0, false}; }
+RowSel strip_groups(int32_t phase, int32_t stride) { return RowSel{0, 0, phase, stride, true}; }
+
+int render_strip(const char* fn, rtx_scene* s, RowSel sel, void* out_dev, uint64_t* counters_dev, void* stream,
+                 bool out8, int32_t nframes = 1, int64_t fstride = 0, int32_t frame0 = -1) {
+    if (int rc = check_camera(fn, s)) return rc;
+    int32_t nrows = sel.nrows;
+    if (sel.groups) {
+        nrows = rtx_group_rows(s->kp.height, sel.phase, sel.stride);
+        if (nrows < 0) return fail(RTX_ERR_INVALID, std::string(fn) + ": need 0 <= phase < stride");
+    } else if (int rc = check_rows(fn, s, sel.row0, sel.nrows)) {
+        return rc;
+    }
     const int64_t block_bytes = (int64_t)nrows * s->kp.ncols * 3 * (out8 ? 1 : 4);
     if (nframes < 1 || nframes > 65535 || (nframes > 1 && fstride < block_bytes) || (!out8 && fstride % 4))
         return fail(RTX_ERR_INVALID, std::string(fn) + ": need 1 <= nframes <= 65535 and frames that do not overlap");
@@ -3507,49 +3542,49 @@ int render_groups(const char* fn, rtx_scene* s, int32_t phase, int32_t stride, v
     if (nrows == 0) return RTX_OK;
     if (!out_dev) return fail(RTX_ERR_INVALID, std::string(fn) + ": null framebuffer");
     L.fb = static_cast<float*>(out_dev);
-    L.row0 = 0;
+    L.row0 = sel.row0;
     L.nrows = nrows;
-    L.gphase = phase;
-    L.gstride = stride;
+    L.gphase = sel.phase;
+    L.gstride = sel.stride;
     L.fstride = nframes > 1 ? fstride : 0;
     return render_launch(s, L, counters_dev, stream, out8, nframes);
 }
 }  // namespace
 
 int rtx_render(rtx_scene* s, int32_t row0, int32_t nrows, float* fb_dev, uint64_t* counters_dev, void* stream) {
-    return render_rows("rtx_render", s, row0, nrows, fb_dev, counters_dev, stream, false);
+    return render_strip("rtx_render", s, strip_rows(row0, nrows), fb_dev, counters_dev, stream, false);
 }
 
 int rtx_render_rgb8(rtx_scene* s, int32_t row0, int32_t nrows, uint8_t* out_dev, uint64_t* counters_dev,
                     void* stream) {
-    return render_rows("rtx_render_rgb8", s, row0, nrows, out_dev, counters_dev, stream, true);
+    return render_strip("rtx_render_rgb8", s, strip_rows(row0, nrows), out_dev, counters_dev, stream, true);
 }
 
 int rtx_render_frames(rtx_scene* s, int32_t row0, int32_t nrows, void* out_dev, int32_t rgb8, int32_t nframes,
                       int64_t frame_stride_bytes, uint64_t* counters_dev, void* stream) {
-    return render_rows("rtx_render_frames", s, row0, nrows, out_dev, counters_dev, stream, rgb8 != 0, nframes,
-                       frame_stride_bytes);
+    return render_strip("rtx_render_frames", s, strip_rows(row0, nrows), out_dev, counters_dev, stream, rgb8 != 0,
+                        nframes, frame_stride_bytes);
 }
 
 int rtx_render_groups_frames(rtx_scene* s, int32_t phase, int32_t stride, void* out_dev, int32_t rgb8,
                              int32_t nframes, int64_t frame_stride_bytes, uint64_t* counters_dev, void* stream) {
-    return render_groups("rtx_render_groups_frames", s, phase, stride, out_dev, counters_dev, stream, rgb8 != 0,
-                         nframes, frame_stride_bytes);
+    return render_strip("rtx_render_groups_frames", s, strip_groups(phase, stride), out_dev, counters_dev, stream,
+                        rgb8 != 0, nframes, frame_stride_bytes);
 }
 
 int rtx_render_sequence(rtx_scene* s, int32_t row0, int32_t nrows, void* out_dev, int32_t rgb8, int32_t frame0,
                         int32_t nframes, int64_t frame_stride_bytes, uint64_t* counters_dev, void* stream) {
     if (frame0 < 0) return fail(RTX_ERR_INVALID, "rtx_render_sequence: frame0 < 0");
-    return render_rows("rtx_render_sequence", s, row0, nrows, out_dev, counters_dev, stream, rgb8 != 0, nframes,
-                       frame_stride_bytes, frame0);
+    return render_strip("rtx_render_sequence", s, strip_rows(row0, nrows), out_dev, counters_dev, stream, rgb8 != 0,
+                        nframes, frame_stride_bytes, frame0);
 }
 
 int rtx_render_groups_sequence(rtx_scene* s, int32_t phase, int32_t stride, void* out_dev, int32_t rgb8,
                                int32_t frame0, int32_t nframes, int64_t frame_stride_bytes, uint64_t* counters_dev,
                                void* stream) {
     if (frame0 < 0) return fail(RTX_ERR_INVALID, "rtx_render_groups_sequence: frame0 < 0");
-    return render_groups("rtx_render_groups_sequence", s, phase, stride, out_dev, counters_dev, stream, rgb8 != 0,
-                         nframes, frame_stride_bytes, frame0);
+    return render_strip("rtx_render_groups_sequence", s, strip_groups(phase, stride), out_dev, counters_dev, stream,
+                        rgb8 != 0, nframes, frame_stride_bytes, frame0);
 }
 
 int32_t rtx_group_rows(int32_t height, int32_t phase, int32_t stride) {
@@ -3564,12 +3599,12 @@ int32_t rtx_group_rows(int32_t height, int32_t phase, int32_t stride) {
 
 int rtx_render_groups(rtx_scene* s, int32_t phase, int32_t stride, float* fb_dev, uint64_t* counters_dev,
                       void* stream) {
-    return render_groups("rtx_render_groups", s, phase, stride, fb_dev, counters_dev, stream, false);
+    return render_strip("rtx_render_groups", s, strip_groups(phase, stride), fb_dev, counters_dev, stream, false);
 }
 
 int rtx_render_groups_rgb8(rtx_scene* s, int32_t phase, int32_t stride, uint8_t* out_dev, uint64_t* counters_dev,
                            void* stream) {
-    return render_groups("rtx_render_groups_rgb8", s, phase, stride, out_dev, counters_dev, stream, true);
+    return render_strip("rtx_render_groups_rgb8", s, strip_groups(phase, stride), out_dev, counters_dev, stream, true);
 }
 
 namespace {
@@ -3842,28 +3877,24 @@ int render_split(rtx_scene* s, Launch L, const KParams* kp, size_t hbytes, hipSt
 
 int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, bool out8, int32_t nframes) {
     const int32_t nrows = L.nrows;
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != s->device)
-        return fail(RTX_ERR_STATE, "rtx_render: the scene lives on device " + std::to_string(s->device) +
-                                       ", the current device is " + std::to_string(cur));
+    if (int rc = check_device("rtx_render", s)) return rc;
     L.counters = reinterpret_cast<unsigned long long*>(counters_dev);
     hipStream_t st = (hipStream_t)stream;
     const bool cnt = counters_dev != nullptr;
     const bool jit = s->kp.jitter != RTX_JITTER_OFF;
     const int sel = (s->has_mesh ? 16 : 0) | (s->has_secondary ? 8 : 0) | (s->has_ext ? 4 : 0) | (cnt ? 2 : 0) | (jit ? 1 : 0);
     const KParams* kp = s->d_kp;
-    const size_t hbytes = (size_t)s->hlevels * 9 * sizeof(float);
+    const size_t hbytes = hstack_bytes(s, 1);
     const int blk = s->has_ext ? kBlock<true> : kBlock<false>;
     const int spp = s->kp.n_dof * s->kp.n_aa * s->kp.n_times;
     const bool spp_mode = use_spp_mode(spp, s->has_ext);
     // pixel mapping: one lane per pixel (8x8 tiles per wave); sample-parallel: blocks of
     // spp_pixels_per_block pixels (rtx_kernels.h render_body_spp)
-    auto blocks = [&](bool sm) {
-        return sm ? ((int64_t)nrows * s->kp.ncols + spp_pixels_per_block(spp, blk) - 1) / spp_pixels_per_block(spp, blk)
-                  : (launch_items(nrows, s->kp.ncols) + blk - 1) / blk;
-    };
-    int64_t nblocks = blocks(spp_mode);
-    if (nblocks > 0x7fffffff || blocks(false) > 0x7fffffff) return fail(RTX_ERR_INVALID, "rtx_render: launch too large");
+    int64_t tblocks, nblocks;
+    if (int rc = tile_blocks("rtx_render", s, nrows, tblocks)) return rc;
+    nblocks = !spp_mode ? tblocks
+                        : ((int64_t)nrows * s->kp.ncols + spp_pixels_per_block(spp, blk) - 1) / spp_pixels_per_block(spp, blk);
+    if (int rc = check_grid("rtx_render", nblocks)) return rc;
     {
 #if RTX_TILE_ORDER == 2  // (experiment builds only): a multiplier coprime to the launch's wave count
         const uint64_t T = (uint64_t)nblocks * (blk / 64) * RTX_PPL;
@@ -3981,21 +4012,11 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
     }
     // the flat-scene kernels use the tile mapping here (their sample-parallel variants
     // are reached through the scene-specialized kernels only)
-    if (spp_mode) nblocks = blocks(false);
     if (int rc = heavy_pass(true)) return rc;
-#define RTX_LAUNCH(M, S, C, J) \
-    hipLaunchKernelGGL((k_render<M, S, false, C, J>), dim3((unsigned)nblocks, (unsigned)nframes), dim3(kBlock<false>), \
-                       0, st, kp, L)
-#define RTX_CASE(n) \
-    case n: RTX_LAUNCH(((n) & 16) != 0, ((n) & 8) != 0, ((n) & 2) != 0, ((n) & 1) != 0); break
-    switch (sel) {
-        RTX_CASE(0); RTX_CASE(1); RTX_CASE(2); RTX_CASE(3);
-        RTX_CASE(8); RTX_CASE(9); RTX_CASE(10); RTX_CASE(11);
-        RTX_CASE(16); RTX_CASE(17); RTX_CASE(18); RTX_CASE(19);
-        RTX_CASE(24); RTX_CASE(25); RTX_CASE(26); RTX_CASE(27);
-    }
-#undef RTX_CASE
-#undef RTX_LAUNCH
+    with_bools([&](auto M, auto S, auto C, auto J) {
+        hipLaunchKernelGGL((k_render<M(), S(), false, C(), J()>), dim3((unsigned)tblocks, (unsigned)nframes),
+                           dim3(kBlock<false>), 0, st, kp, L);
+    }, s->has_mesh, s->has_secondary, cnt, jit);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }
@@ -4022,50 +4043,35 @@ int rtx_intersect(rtx_scene* s, int64_t n, const float* ro, const float* rd, dou
     int rc = view_at(s, (float)time, (float)time, (hipStream_t)stream, view);
     if (rc) return rc;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    const size_t lds = s->has_ext ? (size_t)s->hlevels * 9 * sizeof(float) * 256 : 0;
-#define RTX_ISECT(M, X)                                                                                          \
-    hipLaunchKernelGGL((k_intersect<M, X>), grid, block, lds, (hipStream_t)stream, view, n, ro, rd, (float)time, \
-                       t_dev, obj_dev, mat_dev, normal_dev, position_dev)
-    if (s->has_mesh) { if (s->has_ext) RTX_ISECT(true, true); else RTX_ISECT(true, false); }
-    else { if (s->has_ext) RTX_ISECT(false, true); else RTX_ISECT(false, false); }
-#undef RTX_ISECT
+    const size_t lds = s->has_ext ? hstack_bytes(s, 256) : 0;
+    with_bools([&](auto M, auto X) {
+        hipLaunchKernelGGL((k_intersect<M(), X()>), grid, block, lds, (hipStream_t)stream, view, n, ro, rd, (float)time,
+                           t_dev, obj_dev, mat_dev, normal_dev, position_dev);
+    }, s->has_mesh, s->has_ext);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }
 
 int rtx_render_aov(rtx_scene* s, int32_t row0, int32_t nrows, int32_t frame, float* depth_dev, float* normal_dev,
                    float* position_dev, float* albedo_dev, int32_t* object_dev, int32_t* material_dev, void* stream) {
-    if (!s) return fail(RTX_ERR_INVALID, "rtx_render_aov: null scene");
-    if (!s->cam_set) return fail(RTX_ERR_STATE, "rtx_render_aov: rtx_camera_set was not called");
-    if (row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > s->kp.height)
-        return fail(RTX_ERR_INVALID, "rtx_render_aov: row range outside the image");
+    const char* const fn = "rtx_render_aov";
+    if (int rc = check_camera(fn, s)) return rc;
+    if (int rc = check_rows(fn, s, row0, nrows)) return rc;
     if (!depth_dev && !normal_dev && !position_dev && !albedo_dev && !object_dev && !material_dev)
         return fail(RTX_ERR_INVALID, "rtx_render_aov: no buffer requested (all six pointers are null)");
-    // an ordinary camera holds one window (n_frames 0): frame 0
-    if (frame < 0 || frame >= std::max(s->kp.n_frames, 1))
-        return fail(RTX_ERR_INVALID, "rtx_render_aov: frame " + std::to_string(frame) + " outside the camera's " +
-                                         std::to_string(std::max(s->kp.n_frames, 1)) + " window(s)");
+    if (int rc = check_frame(fn, s, frame)) return rc;
     if (nrows == 0) return RTX_OK;
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != s->device)
-        return fail(RTX_ERR_STATE, "rtx_render_aov: the scene lives on device " + std::to_string(s->device) +
-                                       ", the current device is " + std::to_string(cur));
-    const int blk = s->has_ext ? kBlock<true> : kBlock<false>;
-    const int64_t nblocks = (launch_items(nrows, s->kp.ncols) + blk - 1) / blk;
-    if (nblocks > 0x7fffffff) return fail(RTX_ERR_INVALID, "rtx_render_aov: launch too large");
+    if (int rc = check_device(fn, s)) return rc;
+    int64_t nblocks;
+    if (int rc = tile_blocks(fn, s, nrows, nblocks)) return rc;
     const AovLaunch L{depth_dev, normal_dev, position_dev, albedo_dev, object_dev, material_dev,
                       row0,      nrows,      frame * s->kp.n_times, 0};
-    const size_t lds = s->has_ext ? (size_t)s->hlevels * 9 * sizeof(float) * kBlock<true> : 0;
+    const size_t lds = s->has_ext ? hstack_bytes(s, kBlock<true>) : 0;
     const KParams* kp = s->d_kp;
-    const bool jit = s->kp.jitter != RTX_JITTER_OFF;
-#define RTX_AOV(M, X, J) \
-    hipLaunchKernelGGL((k_aov<M, X, J>), dim3((unsigned)nblocks), dim3(kBlock<X>), lds, (hipStream_t)stream, kp, L)
-#define RTX_AOV_J(M, X) \
-    do { if (jit) RTX_AOV(M, X, true); else RTX_AOV(M, X, false); } while (0)
-    if (s->has_mesh) { if (s->has_ext) RTX_AOV_J(true, true); else RTX_AOV_J(true, false); }
-    else { if (s->has_ext) RTX_AOV_J(false, true); else RTX_AOV_J(false, false); }
-#undef RTX_AOV_J
-#undef RTX_AOV
+    with_bools([&](auto M, auto X, auto J) {
+        hipLaunchKernelGGL((k_aov<M(), X(), J()>), dim3((unsigned)nblocks), dim3(kBlock<X()>), lds, (hipStream_t)stream,
+                           kp, L);
+    }, s->has_mesh, s->has_ext, s->kp.jitter != RTX_JITTER_OFF);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }
@@ -4078,12 +4084,11 @@ int rtx_occluded(rtx_scene* s, int64_t n, const float* ro, const float* rd, cons
     int rc = view_at(s, (float)time, (float)time, (hipStream_t)stream, view);
     if (rc) return rc;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    const size_t lds = s->has_ext ? (size_t)s->hlevels * 9 * sizeof(float) * 256 : 0;
-#define RTX_OCC(M, X) \
-    hipLaunchKernelGGL((k_occluded<M, X>), grid, block, lds, (hipStream_t)stream, view, n, ro, rd, tmax, (float)time, occ)
-    if (s->has_mesh) { if (s->has_ext) RTX_OCC(true, true); else RTX_OCC(true, false); }
-    else { if (s->has_ext) RTX_OCC(false, true); else RTX_OCC(false, false); }
-#undef RTX_OCC
+    const size_t lds = s->has_ext ? hstack_bytes(s, 256) : 0;
+    with_bools([&](auto M, auto X) {
+        hipLaunchKernelGGL((k_occluded<M(), X()>), grid, block, lds, (hipStream_t)stream, view, n, ro, rd, tmax,
+                           (float)time, occ);
+    }, s->has_mesh, s->has_ext);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }
@@ -4125,14 +4130,11 @@ int rtx_cast_rays(rtx_scene* s, int64_t n, const float* ro, const float* rd, con
     const int blk = s->has_ext ? kBlock<true> : kBlock<false>;
     const int ppb = spp_pixels_per_block((int)ns, blk);  // outputs per block (k_cast_rays)
     const int64_t nblocks = (n / group + ppb - 1) / ppb;
-    if (nblocks > 0x7fffffff) return fail(RTX_ERR_INVALID, "rtx_cast_rays: launch too large");
+    if (int rc = check_grid("rtx_cast_rays", nblocks)) return rc;
     if (n == 0) return RTX_OK;
     if (s->has_ext && !(s->has_mesh ? launch_cast_ext_m1 : launch_cast_ext_m0))
         return fail(RTX_ERR_UNSUPPORTED, "rtx_cast_rays: this build holds no hierarchy/texture kernels");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != s->device)
-        return fail(RTX_ERR_STATE, "rtx_cast_rays: the scene lives on device " + std::to_string(s->device) +
-                                       ", the current device is " + std::to_string(cur));
+    if (int rc = check_device("rtx_cast_rays", s)) return rc;
     // the scene-level view, with the hierarchy boxes of the call's time range
     SceneView view;
     hipStream_t st = (hipStream_t)stream;
@@ -4141,35 +4143,27 @@ int rtx_cast_rays(rtx_scene* s, int64_t n, const float* ro, const float* rd, con
     const bool cnt = counters_dev != nullptr;
     if (s->has_ext) {  // precompiled in rtx_kern_ext_m{0,1}.hip
         const int sel = (s->has_secondary ? 8 : 0) | (cnt ? 2 : 0);
-        const size_t lds = (size_t)s->hlevels * 9 * sizeof(float) * kBlock<true>;
+        const size_t lds = hstack_bytes(s, kBlock<true>);
         RTX_HIP(s->has_mesh ? launch_cast_ext_m1(sel, (unsigned)nblocks, lds, st, view, L)
                             : launch_cast_ext_m0(sel, (unsigned)nblocks, lds, st, view, L));
         return RTX_OK;
     }
-#define RTX_CAST(M, S, C) \
-    hipLaunchKernelGGL((k_cast_rays<M, S, false, C>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0, st, view, L)
-#define RTX_CAST_C(M, S) \
-    do { if (cnt) RTX_CAST(M, S, true); else RTX_CAST(M, S, false); } while (0)
-    if (s->has_mesh) { if (s->has_secondary) RTX_CAST_C(true, true); else RTX_CAST_C(true, false); }
-    else { if (s->has_secondary) RTX_CAST_C(false, true); else RTX_CAST_C(false, false); }
-#undef RTX_CAST_C
-#undef RTX_CAST
+    with_bools([&](auto M, auto S, auto C) {
+        hipLaunchKernelGGL((k_cast_rays<M(), S(), false, C()>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0, st,
+                           view, L);
+    }, s->has_mesh, s->has_secondary, cnt);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }
 
 int rtx_render_occlusion(rtx_scene* s, int32_t row0, int32_t nrows, int32_t frame, uint32_t* lights_dev, float* ao_dev,
                          const float* ao_dirs, int32_t n_dirs, double ao_radius, void* stream) {
-    if (!s) return fail(RTX_ERR_INVALID, "rtx_render_occlusion: null scene");
-    if (!s->cam_set) return fail(RTX_ERR_STATE, "rtx_render_occlusion: rtx_camera_set was not called");
-    if (row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > s->kp.height)
-        return fail(RTX_ERR_INVALID, "rtx_render_occlusion: row range outside the image");
+    const char* const fn = "rtx_render_occlusion";
+    if (int rc = check_camera(fn, s)) return rc;
+    if (int rc = check_rows(fn, s, row0, nrows)) return rc;
     if (!lights_dev && !ao_dev)
         return fail(RTX_ERR_INVALID, "rtx_render_occlusion: no buffer requested (both pointers are null)");
-    // an ordinary camera holds one window (n_frames 0): frame 0
-    if (frame < 0 || frame >= std::max(s->kp.n_frames, 1))
-        return fail(RTX_ERR_INVALID, "rtx_render_occlusion: frame " + std::to_string(frame) + " outside the camera's " +
-                                         std::to_string(std::max(s->kp.n_frames, 1)) + " window(s)");
+    if (int rc = check_frame(fn, s, frame)) return rc;
     if (lights_dev && s->view.n_lights > 32)
         return fail(RTX_ERR_INVALID, "rtx_render_occlusion: the light mask holds 32 lights, the scene has " +
                                          std::to_string(s->view.n_lights));
@@ -4192,27 +4186,21 @@ int rtx_render_occlusion(rtx_scene* s, int32_t row0, int32_t nrows, int32_t fram
     if (nrows == 0) return RTX_OK;
     if (s->has_ext && !(s->has_mesh ? launch_occlusion_ext_m1 : launch_occlusion_ext_m0))
         return fail(RTX_ERR_UNSUPPORTED, "rtx_render_occlusion: this build holds no hierarchy/texture kernels");
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != s->device)
-        return fail(RTX_ERR_STATE, "rtx_render_occlusion: the scene lives on device " + std::to_string(s->device) +
-                                       ", the current device is " + std::to_string(cur));
-    const int blk = s->has_ext ? kBlock<true> : kBlock<false>;
-    const int64_t nblocks = (launch_items(nrows, s->kp.ncols) + blk - 1) / blk;
-    if (nblocks > 0x7fffffff) return fail(RTX_ERR_INVALID, "rtx_render_occlusion: launch too large");
+    if (int rc = check_device(fn, s)) return rc;
+    int64_t nblocks;
+    if (int rc = tile_blocks(fn, s, nrows, nblocks)) return rc;
     const KParams* kp = s->d_kp;
     const bool jit = s->kp.jitter != RTX_JITTER_OFF;
     hipStream_t st = (hipStream_t)stream;
     if (s->has_ext) {  // precompiled in rtx_kern_ext_m{0,1}.hip
-        const size_t lds = (size_t)s->hlevels * 9 * sizeof(float) * kBlock<true>;
+        const size_t lds = hstack_bytes(s, kBlock<true>);
         RTX_HIP(s->has_mesh ? launch_occlusion_ext_m1(jit, (unsigned)nblocks, lds, st, kp, L)
                             : launch_occlusion_ext_m0(jit, (unsigned)nblocks, lds, st, kp, L));
         return RTX_OK;
     }
-#define RTX_OCCL(M, J) \
-    hipLaunchKernelGGL((k_occlusion<M, false, J>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0, st, kp, L)
-    if (s->has_mesh) { if (jit) RTX_OCCL(true, true); else RTX_OCCL(true, false); }
-    else { if (jit) RTX_OCCL(false, true); else RTX_OCCL(false, false); }
-#undef RTX_OCCL
+    with_bools([&](auto M, auto J) {
+        hipLaunchKernelGGL((k_occlusion<M(), false, J()>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0, st, kp, L);
+    }, s->has_mesh, jit);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

@@ -894,6 +894,24 @@ __global__ RTX_RENDER_BOUNDS(MESH, SEC, X) void k_render_spp(const KParams* __re
     render_body_spp<MESH, SEC, X, COUNT, JIT>(Pp, L);
 }
 
+// Ray i of n caller-built rays: origins and directions as SoA fp32 [3][n] (rtx_intersect's layout).
+struct Ray {
+    f3 o, d;
+};
+__device__ __forceinline__ Ray soa_ray(const float* ro, const float* rd, int64_t n, int64_t i) {
+    return Ray{mk(ro[i], ro[n + i], ro[2 * n + i]), mk(rd[i], rd[n + i], rd[2 * n + i])};
+}
+
+// The public object id of a hit (-1: a miss; hier: a hierarchy hit, whose sub holds the id).
+__device__ __forceinline__ int32_t hit_oid(const SceneView& S, const Hit& h, bool hier) {
+    return h.obj == -1 ? -1 : hier ? h.sub : S.objs[h.obj].oid;
+}
+
+// The fp64 ray parameter of a hit (+inf: a miss).
+__device__ __forceinline__ double hit_time64(const SceneView& S, const Hit& h, const HHit& hh, f3 o, f3 d, float time) {
+    return h.obj == -1 ? (double)INFINITY : h.obj == kHierHit ? hh.t64 : hit_t64(S, h.obj, h.sub, o, d, time);
+}
+
 template <bool MESH, bool X>
 __global__ __launch_bounds__(256) void k_intersect(SceneView S, int64_t n, const float* __restrict__ ro,
                                                    const float* __restrict__ rd, float time, double* t_out,
@@ -902,8 +920,8 @@ __global__ __launch_bounds__(256) void k_intersect(SceneView S, int64_t n, const
     const HStack hs{hstack + threadIdx.x, (int)blockDim.x};
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const f3 o = mk(ro[i], ro[n + i], ro[2 * n + i]);
-    const f3 d = mk(rd[i], rd[n + i], rd[2 * n + i]);
+    const Ray r = soa_ray(ro, rd, n, i);
+    const f3 o = r.o, d = r.d;
     Tally tl = {};
     HHit hh;
     const Hit h = closest_hit<MESH, X, false>(S, o, d, time, tl, hs, hh);
@@ -916,8 +934,8 @@ __global__ __launch_bounds__(256) void k_intersect(SceneView S, int64_t n, const
         nn = sf.normal;
         pp = sf.position;
     }
-    if (t_out) t_out[i] = !hit ? (double)INFINITY : h.obj == kHierHit ? hh.t64 : hit_t64(S, h.obj, h.sub, o, d, time);
-    if (obj_out) obj_out[i] = !hit ? -1 : h.obj == kHierHit ? h.sub : S.objs[h.obj].oid;
+    if (t_out) t_out[i] = hit_time64(S, h, hh, o, d, time);
+    if (obj_out) obj_out[i] = hit_oid(S, h, h.obj == kHierHit);
     if (mat_out) mat_out[i] = mat;
     if (n_out) { n_out[i] = nn.x; n_out[n + i] = nn.y; n_out[2 * n + i] = nn.z; }
     if (p_out) { p_out[i] = pp.x; p_out[n + i] = pp.y; p_out[2 * n + i] = pp.z; }
@@ -931,10 +949,49 @@ __global__ __launch_bounds__(256) void k_occluded(SceneView S, int64_t n, const 
     const HStack hs{hstack + threadIdx.x, (int)blockDim.x};
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const f3 o = mk(ro[i], ro[n + i], ro[2 * n + i]);
-    const f3 d = mk(rd[i], rd[n + i], rd[2 * n + i]);
+    const Ray r = soa_ray(ro, rd, n, i);
+    const f3 o = r.o, d = r.d;
     Tally tl = {};
     occ[i] = occluded<MESH, X, false>(S, o, d, tmax[i], time, tl, hs) ? 1 : 0;
+}
+
+// The first hit of a lane's pixel (k_aov, k_occlusion). render_body's mapping over rows [row0,
+// row0 + nrows) of the strip: one lane per pixel, an 8x8 tile per wave, the tile's primary bin
+// under render_body's condition. The ray is the one of DOF origin 0, AA origin 0 with that
+// sample's jitter draw (scene.py:57-65), at the motion time P.times[tbase]. closest_hit gets
+// no pixel-in-tile (blane -1): a heavy mesh tile walks its face list, since only a render
+// fills SceneView::mesh_hits. Two steps, so that a ragged-edge lane leaves by a plain return
+// in the kernel before closest_hit's wave votes (one call with the exit inside it made the
+// compiler merge the two paths and branch again): first_pixel gives px and in, the kernel
+// returns on !in, first_hit fills in the rest.
+struct FirstHit {
+    PixelRC px;
+    bool in;
+    int32_t bin;
+    f3 o, d;
+    float time;
+    Hit h;
+    HHit hh;
+};
+
+template <bool X>
+__device__ __forceinline__ FirstHit first_pixel(const KParams& P, int32_t nrows) {
+    FirstHit f;
+    const int32_t ncols = P.ncols;
+    f.px = pixel_rc<kBlock<X>>(ncols, 0);
+    f.in = f.px.r < nrows && f.px.c < ncols;
+    return f;
+}
+
+template <bool MESH, bool X, bool JIT>
+__device__ __forceinline__ void first_hit(const KParams& P, int32_t row0, int32_t tbase, const HStack& hs, Tally& tl,
+                                          FirstHit& f) {
+    f.bin = RTX_TILE == 1 ? primary_bin(P.S, row0 + (f.px.r & ~7), f.px.c & ~7) : -1;
+    const int j = P.height - 1 - (row0 + f.px.r);  // reference row index (y grows upward)
+    f.o = sample_origin<JIT>(P, f.px.c, j, 0, 0);
+    f.d = normalize(sub(pixel_focal(P, f.px.c, j), ld3(P.dof_o)));  // scene.py:58
+    f.time = P.times[tbase];
+    f.h = closest_hit<MESH, X, false>(P.S, f.o, f.d, f.time, tl, hs, f.hh, f.bin, nullptr, -1);
 }
 
 // The per-call block of the first-hit pass (rtx_render_aov): rows [row0, row0 + nrows) of
@@ -957,29 +1014,19 @@ RTX_HD void put3(float* out, int64_t p, f3 v) {
 }
 
 // What the first sample of each pixel sees (no reference counterpart: the attributes of
-// scene.py:86-94's first_intersect for the ray of DOF origin 0, AA origin 0, scene.py:57-65,
-// with that sample's jitter draw, at the frame's first motion time). render_body's mapping:
-// one lane per pixel, an 8x8 tile per wave, ragged edge lanes inactive, the tile's primary
-// bin under render_body's condition. closest_hit gets no pixel-in-tile (blane -1): a heavy
-// mesh tile walks its face list, since only a render fills SceneView::mesh_hits. A tile
-// row's 8 pixels are one contiguous segment of every buffer (32 B, or 96 B for a vector).
+// scene.py:86-94's first_intersect for first_hit's ray at the frame's first motion time). A
+// tile row's 8 pixels are one contiguous segment of every buffer (32 B, or 96 B for a vector).
 template <bool MESH, bool X, bool JIT>
 __global__ __launch_bounds__(kBlock<X>) void k_aov(const KParams* __restrict__ Pp, const AovLaunch L) {
-    constexpr int B = kBlock<X>;
     extern __shared__ float hstack[];  // X: [level][9][thread] (dynamic size)
-    const HStack hs{hstack + threadIdx.x, B};
+    const HStack hs{hstack + threadIdx.x, kBlock<X>};
     const KParams& P = *Pp;
     const int32_t ncols = P.ncols;
-    const PixelRC px = pixel_rc<B>(ncols, 0);
-    if (!(px.r < L.nrows && px.c < ncols)) return;
-    const int32_t bin = RTX_TILE == 1 ? primary_bin(P.S, L.row0 + (px.r & ~7), px.c & ~7) : -1;
-    const int j = P.height - 1 - (L.row0 + px.r);  // reference row index (y grows upward)
-    const f3 o = sample_origin<JIT>(P, px.c, j, 0, 0);
-    const f3 d = normalize(sub(pixel_focal(P, px.c, j), ld3(P.dof_o)));  // scene.py:58
-    const float time = P.times[L.tbase];
     Tally tl = {};
-    HHit hh;
-    const Hit h = closest_hit<MESH, X, false>(P.S, o, d, time, tl, hs, hh, bin, nullptr, -1);
+    FirstHit f = first_pixel<X>(P, L.nrows);
+    if (!f.in) return;
+    first_hit<MESH, X, JIT>(P, L.row0, L.tbase, hs, tl, f);
+    const Hit& h = f.h;
     const bool hit = h.obj != -1;
     const bool hier = X && h.obj == kHierHit;
     Surface sf;
@@ -987,17 +1034,17 @@ __global__ __launch_bounds__(kBlock<X>) void k_aov(const KParams* __restrict__ P
     sf.normal = mk(0.0f, 0.0f, 0.0f);
     sf.mat = -1;
     sf.gobj = -1;
-    if (hit) sf = resolve_hit<MESH, X>(P.S, h, hh, o, d, time);
-    const int64_t p = (int64_t)px.r * ncols + px.c;
-    if (L.depth) L.depth[p] = !hit ? INFINITY : hier ? (float)hh.t64 : h.t32;
+    if (hit) sf = resolve_hit<MESH, X>(P.S, h, f.hh, f.o, f.d, f.time);
+    const int64_t p = (int64_t)f.px.r * ncols + f.px.c;
+    if (L.depth) L.depth[p] = !hit ? INFINITY : hier ? (float)f.hh.t64 : h.t32;
     if (L.position) put3(L.position, p, sf.position);
     if (L.normal) put3(L.normal, p, sf.normal);
-    if (L.object) L.object[p] = !hit ? -1 : hier ? h.sub : P.S.objs[h.obj].oid;
+    if (L.object) L.object[p] = hit_oid(P.S, h, hier);
     if (L.material) L.material[p] = sf.mat;
     if (L.albedo) {  // scene.py:143-146: Plane/AABB hits shade with get_diffuse(position)
         f3 a = mk(0.0f, 0.0f, 0.0f);
         if (hit)
-            a = (X && sf.gobj >= 0) ? get_diffuse(P.S, P.S.objs[sf.gobj], sf.position, time)
+            a = (X && sf.gobj >= 0) ? get_diffuse(P.S, P.S.objs[sf.gobj], sf.position, f.time)
                                     : ld3(RTX_MAT(P.S, sf.mat).diffuse);
         put3(L.albedo, p, a);
     }
@@ -1015,10 +1062,9 @@ struct OccLaunch {
     float dirs[RTX_AO_MAX_DIRS][3];
 };
 
-// Visibility at the first hit of each pixel (no reference counterpart). The ray, the hit and
-// the motion time are k_aov's, statement for statement, and so is the mapping: one lane per
-// pixel, an 8x8 tile per wave, ragged edge lanes inactive, the tile's primary bin, no
-// pixel-in-tile. From the hit's position p and normal n (the values k_aov stores):
+// Visibility at the first hit of each pixel (no reference counterpart). The ray, the hit, the
+// motion time and the mapping are k_aov's: both call first_hit. From the hit's position p and
+// normal n (the values k_aov stores):
 //   lights  bit li = light li's shadow ray from p is free (scene.py:150-167, skip == False).
 //           The tests are regular_lighting's level-0 calls of occluded, argument for argument
 //           (the light's index, the hit's flat object, the tile's shadow-bin word), so they use
@@ -1033,26 +1079,20 @@ struct OccLaunch {
 // leaves before regular_lighting): occluded's wave votes count active lanes only.
 template <bool MESH, bool X, bool JIT>
 __global__ __launch_bounds__(kBlock<X>) void k_occlusion(const KParams* __restrict__ Pp, const OccLaunch L) {
-    constexpr int B = kBlock<X>;
     extern __shared__ float hstack[];  // X: [level][9][thread] (dynamic size)
-    const HStack hs{hstack + threadIdx.x, B};
+    const HStack hs{hstack + threadIdx.x, kBlock<X>};
     const KParams& P = *Pp;
     const int32_t ncols = P.ncols;
-    const PixelRC px = pixel_rc<B>(ncols, 0);
-    if (!(px.r < L.nrows && px.c < ncols)) return;
-    const int32_t bin = RTX_TILE == 1 ? primary_bin(P.S, L.row0 + (px.r & ~7), px.c & ~7) : -1;
-    const int j = P.height - 1 - (L.row0 + px.r);  // reference row index (y grows upward)
-    const f3 o = sample_origin<JIT>(P, px.c, j, 0, 0);
-    const f3 d = normalize(sub(pixel_focal(P, px.c, j), ld3(P.dof_o)));  // scene.py:58
-    const float time = P.times[L.tbase];
     Tally tl = {};
-    HHit hh;
-    const Hit h = closest_hit<MESH, X, false>(P.S, o, d, time, tl, hs, hh, bin, nullptr, -1);
-    const bool hit = h.obj != -1;
+    FirstHit f = first_pixel<X>(P, L.nrows);
+    if (!f.in) return;
+    first_hit<MESH, X, JIT>(P, L.row0, L.tbase, hs, tl, f);
+    const int32_t bin = f.bin;
+    const float time = f.time;
     uint32_t lit = 0u;
     float open = 1.0f;
-    if (hit) {
-        const Surface sf = resolve_hit<MESH, X>(P.S, h, hh, o, d, time);
+    if (f.h.obj != -1) {
+        const Surface sf = resolve_hit<MESH, X>(P.S, f.h, f.hh, f.o, f.d, time);
         if (L.lights != nullptr) {
             cptr<uint32_t> sbm = nullptr;  // the tile's shadow bins (regular_lighting's)
             if (RTX_SHADOW_BINS && bin >= 0 && P.S.bin_shadow != nullptr)  // (wave-uniform)
@@ -1062,7 +1102,7 @@ __global__ __launch_bounds__(kBlock<X>) void k_occlusion(const KParams* __restri
                 const bool point = Lt.type == LIGHT_POINT;
                 const f3 sdir = point ? sub(ld3(Lt.vec), sf.position) : ld3(Lt.negvec);
                 const double t_max = point ? 1.0 : (double)INFINITY;
-                if (!occluded<MESH, X, false>(P.S, sf.position, sdir, t_max, time, tl, hs, nullptr, li, h.obj,
+                if (!occluded<MESH, X, false>(P.S, sf.position, sdir, t_max, time, tl, hs, nullptr, li, f.h.obj,
                                               sbm ? sbm[li] : ~0u))
                     lit |= 1u << li;
             }
@@ -1082,7 +1122,7 @@ __global__ __launch_bounds__(kBlock<X>) void k_occlusion(const KParams* __restri
             open = (float)free_rays / (float)L.n_dirs;
         }
     }
-    const int64_t p = (int64_t)px.r * ncols + px.c;
+    const int64_t p = (int64_t)f.px.r * ncols + f.px.c;
     if (L.lights != nullptr) L.lights[p] = lit;
     if (L.ao != nullptr) L.ao[p] = open;
 }
@@ -1152,9 +1192,8 @@ __global__ RTX_RENDER_BOUNDS(MESH, SEC, X) void k_cast_rays(const SceneView S, c
             const uint32_t g = T == 1 ? (uint32_t)s : (uint32_t)s / (uint32_t)T;
             const int kt = T == 1 ? 0 : (int)((uint32_t)s - g * (uint32_t)T);
             const int64_t i = j * G + g;
-            const f3 o = mk(L.ro[i], L.ro[L.n + i], L.ro[2 * L.n + i]);
-            const f3 d = mk(L.rd[i], L.rd[L.n + i], L.rd[2 * L.n + i]);
-            c = cast_ray<MESH, SEC, X, COUNT>(S, o, d, L.times[kt], tl, fs, hs);
+            const Ray r = soa_ray(L.ro, L.rd, L.n, i);
+            c = cast_ray<MESH, SEC, X, COUNT>(S, r.o, r.d, L.times[kt], tl, fs, hs);
         }
         if (single) {
             if (active) put3(L.rgb, j, c);

@@ -5,7 +5,21 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace rtx {
+// with_bools(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...): the
+// run-time flags of a launch as the template arguments of its kernel variant (every launcher).
+template <class F>
+void with_bools(F&& f) {
+    f();
+}
+template <class F, class... Bs>
+void with_bools(F&& f, bool b, Bs... rest) {
+    if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+
 struct KParams;
 struct Launch;
 

@@ -124,6 +124,86 @@ def sequence_windows(windows):
     return rows
 
 
+# ---- argument checks the render methods share
+def _buffer_names(method, a_noun, known, names):
+    """The buffers asked of ``method`` as a list: each one of ``known``, none twice. ``a_noun``
+    names such a buffer in the messages, with its article ("a feature buffer")."""
+    names = [names] if isinstance(names, str) else list(names)
+    if not names:
+        raise ValueError("%s needs at least one of %s" % (method, known))
+    for n in names:
+        if n not in known:
+            raise ValueError("unknown %s %r (known: %s)" % (a_noun.split(" ", 1)[1], n, ", ".join(known)))
+    if len(set(names)) != len(names):
+        raise ValueError("%s is named twice: %s" % (a_noun, names))
+    return names
+
+
+def _window_frame(windows, frame):
+    """(sequence_windows(windows) or None, frame), the frame inside the windows."""
+    if windows is not None:
+        windows = sequence_windows(windows)
+    frame, n = int(frame), 1 if windows is None else len(windows)
+    if not 0 <= frame < n:
+        raise ValueError("frame %d outside the %d window(s)" % (frame, n))
+    return windows, frame
+
+
+def _row_range(H, row0, nrows):
+    """(row0, nrows) as ints inside an image of H rows; nrows None: down to the last row."""
+    row0 = int(row0)
+    nrows = H - row0 if nrows is None else int(nrows)
+    if row0 < 0 or nrows < 0 or row0 + nrows > H:
+        raise ValueError("rows [%d, %d) outside the image of %d rows" % (row0, row0 + nrows, H))
+    return row0, nrows
+
+
+def _out_dict(out, names, table):
+    """A copy of the caller's ``out`` dict, its tensors checked against table[name] = (shape, dtype)."""
+    out = {} if out is None else dict(out)
+    for n in out:
+        if n not in names:
+            raise ValueError("out holds %r, which is not among the requested buffers %s" % (n, names))
+    for n in names:
+        shape, dtype = table[n]
+        t = out.get(n)
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype
+                              or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError("out[%r] must be a contiguous %s CUDA tensor of shape %s"
+                             % (n, str(dtype).replace("torch.", ""), shape))
+    return out
+
+
+def _out_alloc(out, names, table):
+    """The requested buffers, in order: the caller's where given, new tensors otherwise."""
+    for n in names:
+        if out.get(n) is None:
+            out[n] = torch.empty(table[n][0], dtype=table[n][1], device="cuda")
+    return {n: out[n] for n in names}
+
+
+def _strip_rows(H, row0, nrows, groups):
+    """The row count of a render: of ``groups=(k, n)`` when given, else nrows (None: the rest)."""
+    if groups is not None:
+        k, n = groups
+        nrows = int(N.load().rtx_group_rows(H, int(k), int(n)))
+        if nrows < 0:
+            raise ValueError("groups=(k, n) needs 0 <= k < n")
+    return H - row0 if nrows is None else nrows
+
+
+def _check_fb(out, shape_ok, shape_text):
+    if not shape_ok or out.dtype not in (torch.float32, torch.uint8) or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 or uint8 CUDA tensor " + shape_text)
+
+
+def _counters_ptr(counters):
+    if counters is not None and (counters.numel() < N.RTX_COUNTERS or counters.dtype != torch.int64
+                                 or not counters.is_cuda):
+        raise ValueError("counters must be an int64 CUDA tensor with >= %d entries" % N.RTX_COUNTERS)
+    return C.c_void_p(counters.data_ptr() if counters is not None else 0)
+
+
 def panorama_rays(vc, width, height):
     """An equirectangular panorama about the camera position, a camera the reference lacks,
     as rays for Scene.cast_rays: (origins, directions), numpy float32 [height * width, 3],
@@ -386,25 +466,14 @@ class Scene:
         A uint8 ``out`` (or rgb8=True) gets main.py's PNG bytes from the fused kernel
         (rtx_render_rgb8 / rtx_render_groups_rgb8)."""
         t = self._set_camera(subimage, tasks)
-        if groups is not None:
-            k, n = groups
-            nrows = int(N.load().rtx_group_rows(self.vc.height, int(k), int(n)))
-            if nrows < 0:
-                raise ValueError("groups=(k, n) needs 0 <= k < n")
-        if nrows is None:
-            nrows = self.vc.height - row0
+        nrows = _strip_rows(self.vc.height, row0, nrows, groups)
+        shape = (nrows, t["ncols"], 3)
         if out is None:
-            out = torch.empty((nrows, t["ncols"], 3), dtype=torch.uint8 if rgb8 else torch.float32, device="cuda")
+            out = torch.empty(shape, dtype=torch.uint8 if rgb8 else torch.float32, device="cuda")
         rgb8 = out.dtype == torch.uint8
-        if tuple(out.shape) != (nrows, t["ncols"], 3) or out.dtype not in (torch.float32, torch.uint8) \
-                or not out.is_cuda or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 or uint8 CUDA tensor of shape %s"
-                             % ((nrows, t["ncols"], 3),))
-        if counters is not None and (counters.numel() < N.RTX_COUNTERS or counters.dtype != torch.int64
-                                     or not counters.is_cuda):
-            raise ValueError("counters must be an int64 CUDA tensor with >= %d entries" % N.RTX_COUNTERS)
+        _check_fb(out, tuple(out.shape) == shape, "of shape %s" % (shape,))
+        cnt = _counters_ptr(counters)
         st = stream if stream is not None else torch.cuda.current_stream()
-        cnt = C.c_void_p(counters.data_ptr() if counters is not None else 0)
         suffix = "_rgb8" if rgb8 else ""
         if groups is not None:
             N.call("rtx_render_groups" + suffix, self._native.h, int(groups[0]), int(groups[1]),
@@ -421,16 +490,9 @@ class Scene:
         rtx_render_groups_frames: the frames of one scene state, e.g. a group of
         rtx.distributed.FrameExchange)."""
         t = self._set_camera(0, 1)
-        if groups is not None:
-            nrows = int(N.load().rtx_group_rows(self.vc.height, int(groups[0]), int(groups[1])))
-            if nrows < 0:
-                raise ValueError("groups=(k, n) needs 0 <= k < n")
-        if nrows is None:
-            nrows = self.vc.height - row0
-        if out.dim() != 4 or out.shape[1] < nrows or tuple(out.shape[2:]) != (t["ncols"], 3) \
-                or out.dtype not in (torch.float32, torch.uint8) or not out.is_cuda or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 or uint8 CUDA tensor [frames, >= %d, %d, 3]"
-                             % (nrows, t["ncols"]))
+        nrows = _strip_rows(self.vc.height, row0, nrows, groups)
+        _check_fb(out, out.dim() == 4 and out.shape[1] >= nrows and tuple(out.shape[2:]) == (t["ncols"], 3),
+                  "[frames, >= %d, %d, 3]" % (nrows, t["ncols"]))
         st = stream if stream is not None else torch.cuda.current_stream()
         fn, a, b = ("rtx_render_frames", row0, nrows) if groups is None else ("rtx_render_groups_frames",) + tuple(groups)
         N.call(fn, self._native.h, int(a), int(b), C.c_void_p(out.data_ptr()), int(out.dtype == torch.uint8),
@@ -459,23 +521,13 @@ class Scene:
         if batch < 1:
             raise ValueError("batch must be >= 1")
         H, W = self.vc.height, strip_columns(self.vc.width, 0, 1)[1]
-        if groups is not None:
-            nrows = int(N.load().rtx_group_rows(H, int(groups[0]), int(groups[1])))
-            if nrows < 0:
-                raise ValueError("groups=(k, n) needs 0 <= k < n")
-        if nrows is None:
-            nrows = H - row0
+        nrows = _strip_rows(H, row0, nrows, groups)
         if out is None:
             out = torch.empty((count, nrows, W, 3), dtype=torch.uint8 if rgb8 else torch.float32, device="cuda")
-        if out.dim() != 4 or out.shape[0] != count or out.shape[1] < nrows or tuple(out.shape[2:]) != (W, 3) \
-                or out.dtype not in (torch.float32, torch.uint8) or not out.is_cuda or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 or uint8 CUDA tensor [%d, >= %d, %d, 3]"
-                             % (count, nrows, W))
-        if counters is not None and (counters.numel() < N.RTX_COUNTERS or counters.dtype != torch.int64
-                                     or not counters.is_cuda):
-            raise ValueError("counters must be an int64 CUDA tensor with >= %d entries" % N.RTX_COUNTERS)
+        _check_fb(out, out.dim() == 4 and out.shape[0] == count and out.shape[1] >= nrows
+                  and tuple(out.shape[2:]) == (W, 3), "[%d, >= %d, %d, 3]" % (count, nrows, W))
+        cnt = _counters_ptr(counters)
         st = stream if stream is not None else torch.cuda.current_stream()
-        cnt = C.c_void_p(counters.data_ptr() if counters is not None else 0)
         fn, a, b = ("rtx_render_sequence", row0, nrows) if groups is None else \
             ("rtx_render_groups_sequence",) + tuple(groups)
         stride = int(out.stride(0) * out.element_size())
@@ -504,47 +556,20 @@ class Scene:
         render_sequence takes them) makes it the first time of window ``frame`` instead.
         ``out``: a dict of preallocated contiguous CUDA tensors for some or all of the
         names. Asynchronous on ``stream`` (default: torch's current stream)."""
-        names = [aovs] if isinstance(aovs, str) else list(aovs)
-        if not names:
-            raise ValueError("render_aovs needs at least one of %s" % (AOV_NAMES,))
-        for n in names:
-            if n not in AOV_NAMES:
-                raise ValueError("unknown feature buffer %r (known: %s)" % (n, ", ".join(AOV_NAMES)))
-        if len(set(names)) != len(names):
-            raise ValueError("a feature buffer is named twice: %s" % (names,))
-        if windows is not None:
-            windows = sequence_windows(windows)
-        frame = int(frame)
-        if not 0 <= frame < (1 if windows is None else len(windows)):
-            raise ValueError("frame %d outside the %d window(s)" % (frame, 1 if windows is None else len(windows)))
+        names = _buffer_names("render_aovs", "a feature buffer", AOV_NAMES, aovs)
+        windows, frame = _window_frame(windows, frame)
         H, W = self.vc.height, strip_columns(self.vc.width, subimage, tasks)[1]
-        row0 = int(row0)
-        nrows = H - row0 if nrows is None else int(nrows)
-        if row0 < 0 or nrows < 0 or row0 + nrows > H:
-            raise ValueError("rows [%d, %d) outside the image of %d rows" % (row0, row0 + nrows, H))
-        out = {} if out is None else dict(out)
-        for n in out:
-            if n not in names:
-                raise ValueError("out holds %r, which is not among the requested buffers %s" % (n, names))
-        for n in names:
-            shape = (nrows, W, 3) if n in _AOV_VEC else (nrows, W)
-            dtype = torch.int32 if n in _AOV_INT else torch.float32
-            t = out.get(n)
-            if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype
-                                  or not t.is_cuda or not t.is_contiguous()):
-                raise ValueError("out[%r] must be a contiguous %s CUDA tensor of shape %s"
-                                 % (n, str(dtype).replace("torch.", ""), shape))
+        row0, nrows = _row_range(H, row0, nrows)
+        table = {n: ((nrows, W, 3) if n in _AOV_VEC else (nrows, W), torch.int32 if n in _AOV_INT else torch.float32)
+                 for n in AOV_NAMES}
+        out = _out_dict(out, names, table)
         self._set_camera(subimage, tasks, windows)
-        for n in names:
-            if out.get(n) is None:
-                out[n] = torch.empty((nrows, W, 3) if n in _AOV_VEC else (nrows, W),
-                                     dtype=torch.int32 if n in _AOV_INT else torch.float32, device="cuda")
+        out = _out_alloc(out, names, table)
         st = stream if stream is not None else torch.cuda.current_stream()
-        ptr = [C.c_void_p(out[n].data_ptr() if n in out else 0)
-               for n in ("depth", "normal", "position", "albedo", "object", "material")]
+        ptr = [C.c_void_p(out[n].data_ptr() if n in out else 0) for n in AOV_NAMES]
         if nrows > 0:  # (the tensors of an empty block have no storage to point at)
             N.call("rtx_render_aov", self._native.h, row0, nrows, frame, *ptr, C.c_void_p(st.cuda_stream))
-        return {n: out[n] for n in names}
+        return out
 
     def pick(self, col, row, **camera_kwargs):
         """What pixel (column ``col``, row ``row`` from the top) of the strip shows, as host
@@ -589,24 +614,10 @@ class Scene:
 
         ``out``: a dict of preallocated contiguous CUDA tensors for some or all of the names.
         Asynchronous on ``stream`` (default: torch's current stream)."""
-        names = [buffers] if isinstance(buffers, str) else list(buffers)
-        if not names:
-            raise ValueError("render_occlusion needs at least one of %s" % (OCCLUSION_NAMES,))
-        for n in names:
-            if n not in OCCLUSION_NAMES:
-                raise ValueError("unknown occlusion buffer %r (known: %s)" % (n, ", ".join(OCCLUSION_NAMES)))
-        if len(set(names)) != len(names):
-            raise ValueError("an occlusion buffer is named twice: %s" % (names,))
-        if windows is not None:
-            windows = sequence_windows(windows)
-        frame = int(frame)
-        if not 0 <= frame < (1 if windows is None else len(windows)):
-            raise ValueError("frame %d outside the %d window(s)" % (frame, 1 if windows is None else len(windows)))
+        names = _buffer_names("render_occlusion", "an occlusion buffer", OCCLUSION_NAMES, buffers)
+        windows, frame = _window_frame(windows, frame)
         H, W = self.vc.height, strip_columns(self.vc.width, subimage, tasks)[1]
-        row0 = int(row0)
-        nrows = H - row0 if nrows is None else int(nrows)
-        if row0 < 0 or nrows < 0 or row0 + nrows > H:
-            raise ValueError("rows [%d, %d) outside the image of %d rows" % (row0, row0 + nrows, H))
+        row0, nrows = _row_range(H, row0, nrows)
         if "lights" in names and len(self.lights) > 32:
             raise ValueError("the light mask holds 32 lights, the scene has %d" % len(self.lights))
         dirs, radius = None, math.inf
@@ -633,21 +644,10 @@ class Scene:
                 raise ValueError("ao_radius must be a number") from None
             if not radius > 0.0:  # (NaN too)
                 raise ValueError("ao_radius must be > 0 or inf, got %r" % (ao_radius,))
-        out = {} if out is None else dict(out)
-        for n in out:
-            if n not in names:
-                raise ValueError("out holds %r, which is not among the requested buffers %s" % (n, names))
-        dtypes = dict(lights=torch.int32, ao=torch.float32)
-        for n in names:
-            t = out.get(n)
-            if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (nrows, W) or t.dtype != dtypes[n]
-                                  or not t.is_cuda or not t.is_contiguous()):
-                raise ValueError("out[%r] must be a contiguous %s CUDA tensor of shape %s"
-                                 % (n, str(dtypes[n]).replace("torch.", ""), (nrows, W)))
+        table = dict(lights=((nrows, W), torch.int32), ao=((nrows, W), torch.float32))
+        out = _out_dict(out, names, table)
         self._set_camera(subimage, tasks, windows)
-        for n in names:
-            if out.get(n) is None:
-                out[n] = torch.empty((nrows, W), dtype=dtypes[n], device="cuda")
+        out = _out_alloc(out, names, table)
         st = stream if stream is not None else torch.cuda.current_stream()
         if nrows > 0:  # (the tensors of an empty block have no storage to point at)
             vp = C.c_void_p
@@ -655,7 +655,7 @@ class Scene:
                    vp(out["lights"].data_ptr() if "lights" in out else 0), vp(out["ao"].data_ptr() if "ao" in out else 0),
                    _ptr(dirs, C.c_float) if dirs is not None else None, 0 if dirs is None else int(dirs.shape[0]),
                    radius, vp(st.cuda_stream))
-        return {n: out[n] for n in names}
+        return out
 
     def render(self, subimage: int = 0, tasks: int = 1) -> np.ndarray:
         """scene.py:35-79 — returns float64 (strip_width, height, 3), [column, row-from-bottom]."""
