@@ -1045,14 +1045,19 @@ bool primary_bins(const HostScene& H, const rtx_camera_desc* c, const std::vecto
     BP.ys = c->ys;
     BP.W = W;
     BP.H = Hh;
-    bins_x = (W + 7) / 8;
+    // (a local: the masks' uint32 stores may alias the caller's bins_x, now a CamTables member,
+    // which is then read again at every bin of the marking loops. DepthOfField 4K, this step of
+    // a camera move: 0.078 ms through the reference, 0.039 ms with the local, as the parent's;
+    // profiles/camera_tables/RESULTS.md)
+    const int32_t nbx = (W + 7) / 8;
+    bins_x = nbx;
     const int32_t bins_y = (Hh + 7) / 8;
-    const size_t nb = (size_t)bins_x * bins_y;
+    const size_t nb = (size_t)nbx * bins_y;
     using Rect = BinRect;
     auto rect_of = [&](const double (*pts)[3], int n, Rect& R, double& zlo) { return bins_rect(BP, pts, n, R, zlo); };
     auto mark_in = [&](std::vector<uint32_t>& m, const Rect& R, uint32_t bit) {
         for (int32_t by = R.r0; by <= R.r1; ++by)
-            for (int32_t bx = R.c0; bx <= R.c1; ++bx) m[(size_t)by * bins_x + bx] |= bit;
+            for (int32_t bx = R.c0; bx <= R.c1; ++bx) m[(size_t)by * nbx + bx] |= bit;
     };
     auto mark = [&](const Rect& R, uint32_t bit) { mark_in(objmask, R, bit); };
     auto box_corners = [](const double lo[3], const double hi[3], double (*pts)[3]) {
@@ -1060,7 +1065,7 @@ bool primary_bins(const HostScene& H, const rtx_camera_desc* c, const std::vecto
             for (int a = 0; a < 3; ++a) pts[q][a] = (q >> a) & 1 ? hi[a] : lo[a];
     };
     objmask.assign(nb, 0u);
-    const Rect all{0, bins_x - 1, 0, bins_y - 1};
+    const Rect all{0, nbx - 1, 0, bins_y - 1};
     // moving objects: moved() = fl32(p + speed * time) over the frame's times, padded
     double tlo = INFINITY, thi = -INFINITY;
     for (float t : camera_times(c)) {  // (every frame of a sequence)
@@ -1174,7 +1179,7 @@ bool primary_bins(const HostScene& H, const rtx_camera_desc* c, const std::vecto
         double zlo;
         if (!rect_of(pts, 3, rects[f], zlo)) return true;  // mesh_bins stays 0: walk the BVH
         for (int32_t by = rects[f].r0; by <= rects[f].r1; ++by)
-            for (int32_t bx = rects[f].c0; bx <= rects[f].c1; ++bx) ++count[(size_t)by * bins_x + bx];
+            for (int32_t bx = rects[f].c0; bx <= rects[f].c1; ++bx) ++count[(size_t)by * nbx + bx];
         fz[f] = zlo * (1.0 - 1e-4);
     }
     for (size_t bb = 0; bb < nb; ++bb) start[bb + 1] = start[bb] + count[bb];
@@ -1185,7 +1190,7 @@ bool primary_bins(const HostScene& H, const rtx_camera_desc* c, const std::vecto
     std::stable_sort(order.begin(), order.end(), [&](int32_t a2, int32_t b2) { return fz[a2] < fz[b2]; });
     for (int32_t f : order)  // nearest first within each bin
         for (int32_t by = rects[f].r0; by <= rects[f].r1; ++by)
-            for (int32_t bx = rects[f].c0; bx <= rects[f].c1; ++bx) faces[fill[(size_t)by * bins_x + bx]++] = f;
+            for (int32_t bx = rects[f].c0; bx <= rects[f].c1; ++bx) faces[fill[(size_t)by * nbx + bx]++] = f;
     zmin.resize(faces.size());
     for (size_t q = 0; q < faces.size(); ++q) {
         float z = (float)fz[faces[q]];
@@ -1941,6 +1946,389 @@ void dir_self_boxes(const HostScene& H, std::vector<DSGrid>& grids, double omax)
     }
 }
 
+// ------------------------------------------------------------------ scene and camera tables
+// What rtx_scene_create and rtx_camera_set bind, built on the host with no HIP call: the
+// library uploads the tables and binds device pointers, the tests' host emulation binds the
+// host arrays themselves.
+
+// Some object moves (else the scene-specialized kernels pin a static scene).
+bool any_moving(const HostScene& H) {
+    return std::any_of(H.objs.begin(), H.objs.end(), [](const DObj& o) { return o.has_speed != 0; });
+}
+
+// Light grids for the shadow rays of point lights (option lgrid 0: none, they walk the BVH).
+struct LightGrids {
+    std::vector<DLGrid> grids;
+    std::vector<int32_t> start, faces;
+    std::vector<float> d2;
+    bool build(const HostScene& H) {
+        if (!opt_on(OPT_LGRID) || !light_grids(H, grids, start, faces, d2)) return false;
+        if (faces.empty()) { faces.push_back(0); d2.push_back(0.0f); }  // (no empty table)
+        return true;
+    }
+};
+
+// Where a scene's arrays are: device buffers (rtx_scene_create) or the HostScene's own
+// vectors (the host emulation). lgrid == nullptr: no light grids.
+struct SceneArrays {
+    const DObj* objs = nullptr;
+    const DTri* tris = nullptr;
+    const DTriN* trins = nullptr;
+    const DFaceBox* fboxes = nullptr;
+    const DMat* mats = nullptr;
+    const DLight* lights = nullptr;
+    const DLeaf* leaves = nullptr;
+    const int32_t* tri_orig = nullptr;
+    const uint32_t* texels = nullptr;
+    const float* lut255 = nullptr;
+    const DNodeHot* nodes = nullptr;
+    const DNodeMat* nmat = nullptr;
+    const DLGrid* lgrid = nullptr;
+    const int32_t *lg_start = nullptr, *lg_faces = nullptr;
+    const float* lg_d2 = nullptr;
+};
+
+// The scene-level part of a SceneView (everything but the per-camera tables).
+void bind_scene(const HostScene& H, const SceneArrays& a, SceneView& v) {
+    v.objs = (cptr<DObj>)a.objs;
+    v.tris = (cptr<DTri>)a.tris;
+    v.trins = (cptr<DTriN>)a.trins;
+    v.fboxes = (cptr<DFaceBox>)a.fboxes;
+    v.mats = (cptr<DMat>)a.mats;
+    v.lights = (cptr<DLight>)a.lights;
+    v.leaves = (cptr<DLeaf>)a.leaves;
+    v.tri_orig = (cptr<int32_t>)a.tri_orig;
+    v.n_objs = H.n_objs;
+    v.n_objs_all = (int32_t)H.objs.size();
+    v.n_mats = (int32_t)H.mats.size();
+    v.n_lights = H.n_lights;
+    v.n_plane = H.n_plane; v.n_sphere = H.n_sphere; v.n_box = H.n_box; v.n_mesh = H.n_mesh;
+    v.pow_bits = H.pow_bits;
+    std::memcpy(v.ambient, H.ambient, sizeof(v.ambient));
+    v.nodes = (cptr<DNodeHot>)a.nodes;
+    v.nmat = (cptr<DNodeMat>)a.nmat;
+    v.texels = (cptr<uint32_t>)a.texels;
+    v.lut255 = (cptr<float>)a.lut255;
+    v.n_nodes = (int32_t)H.nodes.size();
+    v.n_tris = (int32_t)H.tris.size();
+    v.n_leaves = (int32_t)H.leaves.size();
+    v.hlevels = H.hlevels;
+    if (a.lgrid) {
+        v.lgrid = (cptr<DLGrid>)a.lgrid;
+        v.lg_start = (cptr<int32_t>)a.lg_start;
+        v.lg_faces = (cptr<int32_t>)a.lg_faces;
+        v.lg_d2 = (cptr<float>)a.lg_d2;
+        v.lgrid_on = 1;
+    }
+}
+
+void bind_dir_grids(SceneView& v, const DSGrid* grids, const void* cells) {
+    v.dsgrid = (cptr<DSGrid>)grids;
+    v.dsg_cells = (cptr<DSCell>)cells;
+    v.dsg_on = 1;
+}
+
+// What depends on the frames' motion-time range [lo, hi] only, not on the camera: the
+// hierarchy bounds and the directional lights' shadow grids (headers, and their cells: on
+// the host, or as the rectangles k_dsg_fill turns into cells in the caller's d_cells).
+// Built again when its key (lo, hi, options dsgrid and dsgrid_min) changes.
+struct TimeTables {
+    bool valid = false;  // the cells are in place (a failed rebuild leaves nothing to reuse)
+    float lo = 0.0f, hi = 0.0f;
+    bool dsg_off = false;  // every shadow ray tests every object
+    double dsg_min = 0.0;  // (dir_shadow_grids reads it)
+    std::vector<DBound> bounds;
+    std::vector<DSGrid> grids;
+    bool grids_on = false;
+    std::vector<DSCell> cells;
+    std::vector<DSRect> rects;  // (until the caller's fill has read them)
+    size_t ncells = 0;
+    void* d_cells = nullptr;  // the caller's device buffer of the cells: it allocates and frees it
+    bool holds(float l, float h) const {
+        return valid && lo == l && hi == h && dsg_off == !opt_on(OPT_DSGRID) && dsg_min == opt(OPT_DSGRID_MIN);
+    }
+    // on_device: the caller fills the cells from `rects` and then sets `valid`
+    void build(const HostScene& H, float l, float h, bool on_device) {
+        valid = false;
+        lo = l; hi = h;
+        dsg_off = !opt_on(OPT_DSGRID);
+        dsg_min = opt(OPT_DSGRID_MIN);
+        bounds.clear();
+        if (!H.nodes.empty())  // hierarchy bounds over the frames' motion-time range
+            bounds = compute_bounds(H.nodes, H.objs, H.tris, l, h);
+        grids.clear();
+        ncells = 0;
+        grids_on = !dsg_off && dir_shadow_grids(H, bounds, l, h, grids, cells, on_device ? &rects : nullptr,
+                                                on_device ? &ncells : nullptr);
+        valid = !on_device;
+    }
+    const void* cells_at() const { return d_cells ? d_cells : cells.data(); }
+};
+
+// Option setup_log: the host time of each step of a setup call, printed to stderr
+// (what == nullptr: never, the host emulation's).
+struct SetupLog {
+    const char* what;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), t = t0;
+    std::string line;
+    explicit SetupLog(const char* w) : what(w) {}
+    size_t staged = 0;  // bytes of camera tables staged by the earlier steps
+    // staged_total: the staging buffer's size after this step (its tables' bytes are logged)
+    void mark(const char* step, size_t staged_total = SIZE_MAX) {
+        if (!what || !opt_on(OPT_SETUP_LOG)) return;
+        const auto n = std::chrono::steady_clock::now();
+        char buf[128];
+        snprintf(buf, sizeof(buf), " %s %.3f", step, std::chrono::duration<double, std::milli>(n - t).count());
+        line += buf;
+        if (staged_total != SIZE_MAX) {
+            snprintf(buf, sizeof(buf), " [%zu B]", staged_total - staged);
+            line += buf;
+            staged = staged_total;
+        }
+        t = n;
+    }
+    ~SetupLog() {
+        if (opt_on(OPT_SETUP_LOG) && !line.empty())
+            fprintf(stderr, "librtx: %s ms:%s (total %.3f)\n", what, line.c_str(),
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+};
+
+// Layout of the camera tables: 256-byte aligned segments of one device buffer. put()
+// records where a table goes and where it comes from (the source must stay alive until
+// write(); p == nullptr: zero-filled); write() fills the pinned buffer once, with no growing
+// host vector to copy (DepthOfField's 1.5 MB of bins: 0.2 ms of reallocation copies).
+struct CamStage {
+    struct Seg {
+        size_t off;
+        const void* p;
+        size_t n;
+        bool dev;  // filled on the device after the upload: not written (nor uploaded)
+    };
+    std::vector<Seg> segs;
+    size_t bytes = 0;
+    size_t put(const void* p, size_t n, bool dev = false) {
+        const size_t off = (bytes + 255) & ~(size_t)255;
+        segs.push_back(Seg{off, p, n, dev});
+        bytes = off + std::max<size_t>(n, 4);
+        return off;
+    }
+    template <class T>
+    size_t put(const std::vector<T>& v) { return put(v.empty() ? nullptr : v.data(), sizeof(T) * v.size()); }
+    size_t size() const { return (bytes + 15) & ~(size_t)15; }  // (whole 16-byte words)
+    // the byte ranges to upload: the segments not filled on the device, merged, in whole
+    // 16-byte words (a segment's next neighbour starts 256-aligned, so the rounding stays
+    // short of it)
+    std::vector<std::pair<size_t, size_t>> runs() const {
+        std::vector<std::pair<size_t, size_t>> r;
+        for (const Seg& g : segs) {
+            if (g.dev) continue;
+            const size_t end = (g.off + std::max<size_t>(g.n, 4) + 15) & ~(size_t)15;
+            if (!r.empty() && r.back().second == g.off) r.back().second = end;
+            else if (!r.empty() && ((r.back().second + 255) & ~(size_t)255) == g.off) r.back().second = end;
+            else r.emplace_back(g.off, end);
+        }
+        return r;
+    }
+    void write(char* h) const {
+        for (const Seg& g : segs) {
+            if (g.p) memcpy(h + g.off, g.p, g.n);
+            else if (!g.dev) memset(h + g.off, 0, std::max<size_t>(g.n, 4));
+        }
+    }
+};
+
+// Every per-camera table of a scene: which ones the camera gets (the predicates), the
+// tables themselves (put() keeps pointers: they live here until the caller has written the
+// staging buffer), their layout in one buffer, and the KParams / SceneView pointers into it.
+// The caller allocates the buffer (st.size() bytes), binds, writes the staged part
+// (st.write(), st.runs()) and fills the segments staged last, which no host table backs:
+// the face lists of device-built bins (o_bfaces, o_bz), the heavy tiles' hits (o_mhits: the
+// chunk pass before each frame), the shadow bins (o_bshadow, from sbs) and the tile times
+// (o_ttime: a measured frame).
+struct CamTables {
+    // Stage 1 of device-built face bins of the scene's one mesh (rtx_bins.hip): the bins'
+    // starts, the number of (bin, face) pairs and mesh_bins. Empty: the host builds the lists.
+    using DevFaces = std::function<int(int32_t bins_x, std::vector<int32_t>& start, int32_t* npairs, int32_t* mesh_bins)>;
+
+    bool replay = false;     // the camera replays a noise table
+    bool pself = false;      // plane self-test limits
+    bool bins = false;       // primary-ray bins
+    bool dev_faces = false;  // the mesh's face bins are built on the device
+    bool heavy = false;      // heavy tiles' chunks
+    bool sbins = false;      // shadow bins
+    bool tsched = false;     // the measured tile schedule
+    bool po = false;         // the primary rays' origin-only terms
+
+    // (the order the tables are built in: they are freed in the reverse order, the large
+    // mask vectors together, after the upload)
+    std::vector<float> times;
+    CamStage st;
+    std::vector<DBox> boxes;
+    std::vector<float> pself_lim;
+    std::vector<DSGrid> grids;
+    std::vector<int32_t> ident, bstart, bfaces;
+    std::vector<float> bz;
+    std::vector<uint32_t> bmask, brmask;  // bmask: [object masks | root masks]; brmask: the latter's source
+    std::vector<int32_t> bheavy;
+    std::vector<int2> hitems;
+    SbScene sbs;
+    int32_t bins_x = 0, mesh_bins = 0, dev_pairs = 0;
+    int64_t tiles = 0;
+
+    size_t host_bytes = 0;  // the staged part: what precedes the segments filled later
+    size_t o_xs = 0, o_ys = 0, o_dof = 0, o_aa = 0, o_times = 0, o_noise = 0, o_bounds = 0, o_pself = 0, o_dsg = 0;
+    size_t o_bstart = 0, o_bfaces = 0, o_bz = 0, o_bmask = 0, o_bheavy = 0, o_hitems = 0, o_mhits = 0, o_sbs = 0;
+    size_t o_bshadow = 0, o_tperm = 0, o_ttime = 0, o_kp = 0;
+
+    // times_: camera_times(c), which the caller has for the time range
+    int build(const HostScene& H, const rtx_camera_desc* c, std::vector<float> times_, const TimeTables& tr,
+              const DevFaces& dev1, SetupLog& slog) {
+        const size_t nsamp = (size_t)c->n_dof * c->n_aa;
+        const double omax = camera_origin_bound(c);
+        times = std::move(times_);
+        o_xs = st.put(c->xs, sizeof(float) * c->ncols);
+        o_ys = st.put(c->ys, sizeof(float) * c->height);
+        o_dof = st.put(c->dof_origins, sizeof(float) * 3 * c->n_dof);
+        o_aa = st.put(c->aa_origins, sizeof(float) * 3 * nsamp);
+        o_times = st.put(times);
+        replay = c->jitter == RTX_JITTER_REPLAY;
+        if (replay) o_noise = st.put(c->noise, sizeof(float) * 3 * (size_t)c->ncols * c->height * nsamp);
+        slog.mark("tables", st.size());
+        if (!H.nodes.empty()) {
+            boxes = split_bounds(tr.bounds);
+            o_bounds = st.put(boxes);
+        }
+        // self tests of planes (option self_skip 0: none). Scenes with secondary rays get none:
+        // MirrorRefraction measured 1.4 % slower with them (most of its shadow rays leave
+        // deeper levels, which pay the check and never skip), TSP 3 % and TM 2 % faster
+        // (profiles/r04/plane_self/)
+        pself = opt_on(OPT_SELF_SKIP) && H.n_plane > 0 && !H.lights.empty() && !H.has_secondary;
+        if (pself) {
+            pself_lim = plane_self_limits(H, omax);
+            o_pself = st.put(pself_lim);
+        }
+        if (tr.grids_on) {  // the grid headers with this camera's self-test marks
+            grids = tr.grids;
+            dir_self_boxes(H, grids, omax);
+            o_dsg = st.put(grids);
+        }
+        slog.mark("self tests", st.size());
+        bins = opt_on(OPT_BINS) && primary_bins(H, c, tr.bounds, bstart, bfaces, bz, bmask, brmask, bins_x, mesh_bins,
+                                                dev1 && opt_on(OPT_DEV_BINS) ? &dev_faces : nullptr);
+        if (bins && dev_faces) {
+            if (int rc = dev1(bins_x, bstart, &dev_pairs, &mesh_bins)) return rc;
+            dev_faces = dev_pairs > 0;
+            slog.mark("face bins: counts read back");
+        }
+        if (bins) {
+            if (bfaces.empty() && !dev_faces) { bfaces.push_back(0); bz.push_back(0.0f); }
+            bmask.insert(bmask.end(), brmask.begin(), brmask.end());
+            o_bstart = st.put(bstart);
+            if (!dev_faces) {  // (the device-filled lists go last: below)
+                o_bfaces = st.put(bfaces);
+                o_bz = st.put(bz);
+            }
+            o_bmask = st.put(bmask);
+        }
+        heavy = bins && mesh_bins && !H.has_ext && opt_on(OPT_HEAVY_TILES) && heavy_chunks(bstart, bheavy, hitems);
+        if (heavy) {
+            o_bheavy = st.put(bheavy);
+            o_hitems = st.put(hitems);
+        }
+        // shadow bins (option shadow_bins 0: none): flat scenes of primary and shadow rays. Scenes
+        // with secondary rays get none, as with the planes' self tests: most of their shadow rays
+        // leave deeper levels, which would pay the check and never skip
+        sbins = bins && opt_on(OPT_SHADOW_BINS) && (!H.has_secondary || opt(OPT_SHADOW_BINS) >= 2) && !H.has_mesh &&
+                !H.has_ext && shadow_bins_scene(H, c, bins_x, 1.0, sbs);
+        if (sbins) o_sbs = st.put(&sbs, sizeof(sbs));
+        slog.mark("bins", st.size());
+        // the measured tile schedule (tile_schedule): identity order until measured
+        tsched = opt_on(OPT_TILE_SCHED) && !H.has_ext && (H.has_secondary || H.has_mesh);
+        int64_t nw = 0;  // the tiles, in whole blocks of waves
+        if (tsched) {
+            const int64_t wpb = kBlock<false> / 64;
+            tiles = (int64_t)((c->ncols + 7) / 8) * ((c->height + 7) / 8);
+            nw = (tiles + wpb - 1) / wpb * wpb;
+            ident.resize((size_t)nw);
+            std::iota(ident.begin(), ident.end(), 0);
+            o_tperm = st.put(ident);
+        }
+        o_kp = st.put(nullptr, sizeof(KParams));
+        // the segments filled after the upload, last: the host stages (and uploads) only what
+        // precedes them
+        host_bytes = st.size();
+        if (dev_faces) {
+            o_bfaces = st.put(nullptr, sizeof(int32_t) * dev_pairs, true);
+            o_bz = st.put(nullptr, sizeof(float) * dev_pairs, true);
+        }
+        if (heavy) o_mhits = st.put(nullptr, sizeof(uint2) * 64 * hitems.size(), true);
+        if (sbins) o_bshadow = st.put(nullptr, sizeof(uint32_t) * (size_t)sbs.bins_x * sbs.bins_y * sbs.NL, true);
+        if (tsched) o_ttime = st.put(nullptr, sizeof(uint32_t) * nw, true);
+        slog.mark("tile schedule", st.size());
+        // one sample, no jitter, static scene: every primary ray starts at aa_o[0], so its
+        // origin-only plane and sphere terms are per-frame constants (closest_hit's fp32
+        // operations, here once; RTX_PRIM_ORIGIN kernels read them)
+        // (flat primary + shadow scenes: TwoSpheresPlane 24.09 -> 23.59 us, TorusMesh -0.6 %;
+        // MirrorRefraction measured 1 % slower with them, profiles/r04/prim_origin/)
+        po = c->n_dof == 1 && c->n_aa == 1 && c->jitter == RTX_JITTER_OFF && !any_moving(H) && !H.has_ext &&
+             !H.has_secondary && H.n_plane <= 4 && H.n_sphere <= 16 && opt_on(OPT_PRIM_ORIGIN);
+        return RTX_OK;
+    }
+
+    // Every table pointer of k (k.S holds the scene-level view) into the buffer at D.
+    void bind(KParams& k, char* D, const HostScene& H, const rtx_camera_desc* c, const TimeTables& tr) const {
+        k.xs = (cptr<float>)(D + o_xs);
+        k.ys = (cptr<float>)(D + o_ys);
+        k.dof_o = (cptr<float>)(D + o_dof);
+        k.aa_o = (cptr<float>)(D + o_aa);
+        k.times = (cptr<float>)(D + o_times);
+        k.noise = replay ? (cptr<float>)(D + o_noise) : nullptr;
+        if (!H.nodes.empty()) bind_boxes(k.S, (const DBox*)(D + o_bounds), H.nodes.size());
+        if (pself) k.S.plane_self = (cptr<float>)(D + o_pself);
+        if (tr.grids_on) bind_dir_grids(k.S, (const DSGrid*)(D + o_dsg), tr.cells_at());
+        if (bins) {
+            k.S.bin_objmask = (cptr<uint32_t>)(D + o_bmask);
+            k.S.bin_rootmask = (cptr<uint32_t>)(D + o_bmask) + brmask.size();
+            k.S.mesh_bins = mesh_bins;
+            k.S.bin_start = (cptr<int32_t>)(D + o_bstart);
+            k.S.bin_faces = (cptr<int32_t>)(D + o_bfaces);
+            k.S.bin_zmin = (cptr<float>)(D + o_bz);
+            k.S.bins_x = bins_x;
+            k.S.bins_on = 1;
+        }
+        if (sbins) k.S.bin_shadow = (cptr<uint32_t>)(D + o_bshadow);
+        if (heavy) {
+            k.S.bin_heavy = (cptr<int32_t>)(D + o_bheavy);
+            k.S.mesh_hits = reinterpret_cast<const uint2*>(D + o_mhits);
+        }
+        if (po) {
+            const f3 o = mk(c->aa_origins[0], c->aa_origins[1], c->aa_origins[2]);
+            int oi = 0;
+            for (int q = 0; q < H.n_plane; ++q, ++oi) {
+                const DObj& ob = H.objs[oi];
+                k.po_pnum[q] = dot(sub(moved(ob, ob.a, 0.0f), o), ld3(ob.b));
+            }
+            for (int q = 0; q < H.n_sphere; ++q, ++oi) {
+                const DObj& ob = H.objs[oi];
+                const f3 oc = sub(o, moved(ob, ob.a, 0.0f));
+                k.po_soc[q][0] = oc.x; k.po_soc[q][1] = oc.y; k.po_soc[q][2] = oc.z;
+                k.po_sq[q] = dot(oc, oc);
+            }
+            k.po_valid = 1;
+        }
+        if (tsched) {
+            k.tile_perm = (cptr<int32_t>)(D + o_tperm);
+            k.tile_time = reinterpret_cast<unsigned int*>(D + o_ttime);
+            k.tile_n = (int32_t)tiles;
+        }
+        // the camera block's copies of the first DOF and AA origins (rtx_kernels.h KParams),
+        // refreshed with the tables on every upload
+        set3(k.dof0, c->dof_origins);
+        set3(k.aa0, c->aa_origins);
+    }
+};
+
 }  // namespace
 
 // ------------------------------------------------------------------ scene-specialized kernels
@@ -1968,7 +2356,7 @@ SceneTraits scene_traits(const HostScene& H) {
     for (const DObj& o : H.objs)
         if (o.type == RTX_MESH) { ++n_m; n_fc += o.face_cull ? 1 : 0; }
     t.fc_mode = n_fc == 0 ? 0 : n_fc == n_m ? 1 : 2;
-    for (const DObj& o : H.objs) t.any_speed = t.any_speed || o.has_speed;
+    t.any_speed = any_moving(H);
     t.uniform_hard = H.uniform_hard >= 0 ? H.uniform_hard : -1;
     for (size_t i = 0; i < H.lights.size() && i < 32; ++i)
         if (H.lights[i].type == LIGHT_DIRECTIONAL) t.light_dir_mask |= 1u << i;
@@ -2043,11 +2431,6 @@ bool use_spp_mode(int spp, bool ext) {
     return ext && spp >= opt(OPT_SPP_MIN);
 }
 
-// Host-computed origin terms of primary rays (RTX_PRIM_ORIGIN kernels; option prim_origin).
-bool prim_origin_enabled() { return opt_on(OPT_PRIM_ORIGIN); }
-
-// The measured tile schedule (tile_schedule; option tile_sched).
-bool tile_sched_enabled() { return opt_on(OPT_TILE_SCHED); }
 // Threads per block of a scene-specialized tile-mapped kernel (one 8x8 tile per wave).
 // The secondary-ray and mesh kernels -- the tile-scheduled kinds, whose waves differ most in
 // length -- run in one-wave blocks (option tile_block, 64 or 256): MirrorRefraction 36.7 ->
@@ -2666,12 +3049,10 @@ struct rtx_scene {
     bool has_mesh = false, has_secondary = false, has_ext = false;
     SceneTraits traits;  // what the scene-specialized kernels pin
     int32_t hlevels = 0;
-    // host copies for the per-time-range hierarchy bounds
-    std::vector<DNode> h_nodes;
-    std::vector<DObj> h_objs;
-    std::vector<DTri> h_tris;
+    // the converted scene, less the arrays only the device reads (rtx_scene_create clears
+    // them): what the per-camera tables and the per-time-range hierarchy bounds are built from
+    HostScene H;
     std::vector<DBox> h_bounds_abi;
-    HostScene h_bins;   // objs/tris and type counts, for the camera's primary-ray face bins
     void* d_lgrid = nullptr;        // light grids (per scene: lights and mesh are static)
     void* d_lg_start = nullptr;
     void* d_lg_faces = nullptr;
@@ -2700,15 +3081,9 @@ struct rtx_scene {
     char* h_cam = nullptr;  // pinned bounce buffer of the camera uploads (pinned_copy)
     size_t h_cam_cap = 0;
     KParams* d_kp = nullptr;  // (inside d_cam)
-    // per frame time range [tlo, thi] (not per camera): the hierarchy bounds and the
-    // directional lights' shadow-grid headers and cells (the cells in their own buffer)
-    bool tr_valid = false;
-    float tr_lo = 0.0f, tr_hi = 0.0f;
-    std::vector<DBound> tr_bounds;
-    std::vector<DSGrid> tr_grids;
-    bool tr_grids_on = false, tr_dsg_off = false;
-    double tr_dsg_min = 0.0;
-    void* d_dsg_cells = nullptr;
+    // per frame time range (not per camera): the hierarchy bounds and the directional
+    // lights' shadow-grid headers and cells (the cells in their own device buffer, tr.d_cells)
+    TimeTables tr;
     // the kernel resolved for each (counters, jitter, sample-parallel) variant of the
     // current camera: looked up (and compiled) once per camera, not per frame; nullptr
     // after a lookup means the generic kernel; 16-27: the split hierarchy passes
@@ -2831,7 +3206,7 @@ void free_scene(rtx_scene* s) {
     free_camera(s);
     (void)hipFree(s->d_cam);
     (void)hipHostFree(s->h_cam);
-    (void)hipFree(s->d_dsg_cells);
+    (void)hipFree(s->tr.d_cells);
     (void)hipFree(s->d_scratch);
     (void)hipFree(s->d_mb);
     (void)hipFree(s->d_mb2);
@@ -2853,81 +3228,6 @@ void free_scene(rtx_scene* s) {
 }  // namespace
 
 namespace {
-// Option setup_log: the host time of each step of a setup call, printed to stderr.
-struct SetupLog {
-    const char* what;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), t = t0;
-    std::string line;
-    explicit SetupLog(const char* w) : what(w) {}
-    size_t staged = 0;  // bytes of camera tables staged by the earlier steps
-    // staged_total: the staging buffer's size after this step (its tables' bytes are logged)
-    void mark(const char* step, size_t staged_total = SIZE_MAX) {
-        if (!opt_on(OPT_SETUP_LOG)) return;
-        const auto n = std::chrono::steady_clock::now();
-        char buf[128];
-        snprintf(buf, sizeof(buf), " %s %.3f", step, std::chrono::duration<double, std::milli>(n - t).count());
-        line += buf;
-        if (staged_total != SIZE_MAX) {
-            snprintf(buf, sizeof(buf), " [%zu B]", staged_total - staged);
-            line += buf;
-            staged = staged_total;
-        }
-        t = n;
-    }
-    ~SetupLog() {
-        if (opt_on(OPT_SETUP_LOG) && !line.empty())
-            fprintf(stderr, "librtx: %s ms:%s (total %.3f)\n", what, line.c_str(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    }
-};
-
-// Layout of the camera tables: 256-byte aligned segments of one device buffer. put()
-// records where a table goes and where it comes from (the source must stay alive until
-// write(); p == nullptr: zero-filled); write() fills the pinned buffer once, with no growing
-// host vector to copy (DepthOfField's 1.5 MB of bins: 0.2 ms of reallocation copies).
-struct CamStage {
-    struct Seg {
-        size_t off;
-        const void* p;
-        size_t n;
-        bool dev;  // filled on the device after the upload: not written (nor uploaded)
-    };
-    std::vector<Seg> segs;
-    size_t bytes = 0;
-    size_t put(const void* p, size_t n, bool dev = false) {
-        const size_t off = (bytes + 255) & ~(size_t)255;
-        segs.push_back(Seg{off, p, n, dev});
-        bytes = off + std::max<size_t>(n, 4);
-        return off;
-    }
-    template <class T>
-    size_t put(const std::vector<T>& v) { return put(v.empty() ? nullptr : v.data(), sizeof(T) * v.size()); }
-    size_t size() const { return (bytes + 15) & ~(size_t)15; }  // (whole 16-byte words)
-    // the byte ranges to upload: the segments not filled on the device, merged, in whole
-    // 16-byte words (a segment's next neighbour starts 256-aligned, so the rounding stays
-    // short of it)
-    std::vector<std::pair<size_t, size_t>> runs() const {
-        std::vector<std::pair<size_t, size_t>> r;
-        for (const Seg& g : segs) {
-            if (g.dev) continue;
-            const size_t end = (g.off + std::max<size_t>(g.n, 4) + 15) & ~(size_t)15;
-            if (!r.empty() && r.back().second == g.off) r.back().second = end;
-            else if (!r.empty() && ((r.back().second + 255) & ~(size_t)255) == g.off) r.back().second = end;
-            else r.emplace_back(g.off, end);
-        }
-        return r;
-    }
-    void write(char* h) const {
-        for (const Seg& g : segs) {
-            if (g.p) memcpy(h + g.off, g.p, g.n);
-            else if (!g.dev) memset(h + g.off, 0, std::max<size_t>(g.n, 4));
-        }
-    }
-};
-
-}  // namespace
-
-namespace {
 // Stage 1 of the device face bins of the scene's one mesh (option dev_bins; rtx_bins.hip):
 // uploads the pixel tables, bins every face, and reads the bins' face counts back (a copy
 // kernel into the mapped pinned buffer: no copy engine) into start (prefix sums, nb + 1).
@@ -2935,7 +3235,7 @@ namespace {
 // the host). Leaves the faces' order in the scene's scratch for stage 2.
 int mesh_bins_dev1(rtx_scene* s, const rtx_camera_desc* c, int32_t bins_x, std::vector<int32_t>& start,
                    int32_t* npairs, int32_t* mesh_bins, SetupLog& slog) {
-    const HostScene& H = s->h_bins;
+    const HostScene& H = s->H;
     const DObj& m = H.objs[H.n_plane + H.n_sphere + H.n_box];
     const int32_t n = m.tri_count, W = c->ncols, Hh = c->height;
     const int32_t nb = bins_x * ((Hh + 7) / 8);
@@ -2989,7 +3289,7 @@ int mesh_bins_dev1(rtx_scene* s, const rtx_camera_desc* c, int32_t bins_x, std::
 
 // Stage 2: the bins' face lists and depth bounds into the camera buffer.
 int mesh_bins_dev2(rtx_scene* s, int32_t bins_x, int32_t nb, int32_t npairs, int32_t* faces, float* zmin) {
-    const HostScene& H = s->h_bins;
+    const HostScene& H = s->H;
     const int32_t n = H.objs[H.n_plane + H.n_sphere + H.n_box].tri_count;
     if (int rc = grow(&s->d_mb2, &s->mb2_cap, mesh_bins_bytes2(n, npairs))) return rc;
     RTX_HIP(mesh_bins_stage2(s->mbd, n, bins_x, nb, npairs, s->d_mb2, faces, zmin, nullptr));
@@ -3073,10 +3373,10 @@ int32_t rtx_jit_modules(void) {
 int rtx_scene_create(const rtx_scene_desc* desc, rtx_scene** out) {
     if (!out) return fail(RTX_ERR_INVALID, "rtx_scene_create: null argument");
     *out = nullptr;
-    HostScene H;
-    int rc = convert_scene(desc, H);
-    if (rc) return rc;
     rtx_scene* s = new rtx_scene();
+    HostScene& H = s->H;
+    int rc = convert_scene(desc, H);
+    if (rc) { delete s; return rc; }
     if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(RTX_ERR_HIP, "hipGetDevice failed"); }
     if ((rc = upload(&s->d_objs, H.objs)) || (rc = upload(&s->d_tris, H.tris)) || (rc = upload(&s->d_trins, H.trins)) ||
         (rc = upload(&s->d_fboxes, H.fboxes)) ||
@@ -3101,70 +3401,55 @@ int rtx_scene_create(const rtx_scene_desc* desc, rtx_scene** out) {
     s->hlevels = H.hlevels;
     s->traits = scene_traits(H);
     s->jit_baked = jit_baked_records(H.objs, H.mats, H.lights);
-    {  // primary-ray bins (per camera, rtx_camera_set)
-        s->h_bins.objs = H.objs;
-        if (H.n_mesh == 1) s->h_bins.tris = H.tris;
-        s->h_bins.n_plane = H.n_plane; s->h_bins.n_sphere = H.n_sphere;
-        s->h_bins.n_box = H.n_box; s->h_bins.n_mesh = H.n_mesh;
-        s->h_bins.lights = H.lights;  // and the shadow grids of directional lights
-        s->h_bins.nodes = H.nodes;
-    }
     if (!H.nodes.empty()) {
-        s->h_nodes = H.nodes;
         s->csg_tables = jit_csg_tables(H.nodes);
-        s->h_objs = H.objs;
-        s->h_tris = H.tris;
         if ((rc = upload(&s->d_bounds_abi, std::vector<DBox>(3 * H.nodes.size())))) {
             free_scene(s);
             return rc;
         }
     }
-    SceneView& v = s->view;
-    v.objs = (cptr<DObj>)s->d_objs;
-    v.tris = (cptr<DTri>)s->d_tris;
-    v.trins = (cptr<DTriN>)s->d_trins;
-    v.fboxes = (cptr<DFaceBox>)s->d_fboxes;
-    v.mats = (cptr<DMat>)s->d_mats;
-    v.lights = (cptr<DLight>)s->d_lights;
-    v.leaves = (cptr<DLeaf>)s->d_leaves;
-    v.tri_orig = (cptr<int32_t>)s->d_tri_orig;
-    v.n_objs = H.n_objs;
-    v.n_objs_all = (int32_t)H.objs.size();
-    v.n_mats = (int32_t)H.mats.size();
-    v.n_lights = H.n_lights;
-    v.n_plane = H.n_plane; v.n_sphere = H.n_sphere; v.n_box = H.n_box; v.n_mesh = H.n_mesh;
-    v.pow_bits = H.pow_bits;
-    std::memcpy(v.ambient, H.ambient, sizeof(v.ambient));
-    v.nodes = (cptr<DNodeHot>)s->d_nodes;
-    v.nmat = (cptr<DNodeMat>)s->d_nmat;
-    v.texels = (cptr<uint32_t>)s->d_texels;
-    v.lut255 = (cptr<float>)s->d_lut;
-    v.n_nodes = (int32_t)H.nodes.size();
-    v.n_tris = (int32_t)H.tris.size();
-    v.n_leaves = (int32_t)H.leaves.size();
-    v.hlevels = H.hlevels;
-    {  // light grids for the shadow rays of point lights (option lgrid 0: walk the BVH)
-        std::vector<DLGrid> grids;
-        std::vector<int32_t> gstart, gfaces;
-        std::vector<float> gd2;
-        if (opt_on(OPT_LGRID) && light_grids(H, grids, gstart, gfaces, gd2)) {
-            if (gfaces.empty()) { gfaces.push_back(0); gd2.push_back(0.0f); }
-            if (opt_on(OPT_SETUP_LOG))
-                fprintf(stderr, "librtx: light grids: %zu grids %zu B, starts %zu B, faces %zu B, d2 %zu B\n", grids.size(),
-                        sizeof(DLGrid) * grids.size(), sizeof(int32_t) * gstart.size(), sizeof(int32_t) * gfaces.size(),
-                        sizeof(float) * gd2.size());
-            if ((rc = upload(&s->d_lgrid, grids)) || (rc = upload(&s->d_lg_start, gstart)) ||
-                (rc = upload(&s->d_lg_faces, gfaces)) || (rc = upload(&s->d_lg_d2, gd2))) {
-                free_scene(s);
-                return rc;
-            }
-            v.lgrid = (cptr<DLGrid>)s->d_lgrid;
-            v.lg_start = (cptr<int32_t>)s->d_lg_start;
-            v.lg_faces = (cptr<int32_t>)s->d_lg_faces;
-            v.lg_d2 = (cptr<float>)s->d_lg_d2;
-            v.lgrid_on = 1;
+    LightGrids lg;
+    const bool lgrid = lg.build(H);
+    if (lgrid) {
+        if (opt_on(OPT_SETUP_LOG))
+            fprintf(stderr, "librtx: light grids: %zu grids %zu B, starts %zu B, faces %zu B, d2 %zu B\n", lg.grids.size(),
+                    sizeof(DLGrid) * lg.grids.size(), sizeof(int32_t) * lg.start.size(), sizeof(int32_t) * lg.faces.size(),
+                    sizeof(float) * lg.d2.size());
+        if ((rc = upload(&s->d_lgrid, lg.grids)) || (rc = upload(&s->d_lg_start, lg.start)) ||
+            (rc = upload(&s->d_lg_faces, lg.faces)) || (rc = upload(&s->d_lg_d2, lg.d2))) {
+            free_scene(s);
+            return rc;
         }
     }
+    SceneArrays a;
+    a.objs = (const DObj*)s->d_objs;
+    a.tris = (const DTri*)s->d_tris;
+    a.trins = (const DTriN*)s->d_trins;
+    a.fboxes = (const DFaceBox*)s->d_fboxes;
+    a.mats = (const DMat*)s->d_mats;
+    a.lights = (const DLight*)s->d_lights;
+    a.leaves = (const DLeaf*)s->d_leaves;
+    a.tri_orig = (const int32_t*)s->d_tri_orig;
+    a.texels = (const uint32_t*)s->d_texels;
+    a.lut255 = (const float*)s->d_lut;
+    a.nodes = (const DNodeHot*)s->d_nodes;
+    a.nmat = (const DNodeMat*)s->d_nmat;
+    if (lgrid) {
+        a.lgrid = (const DLGrid*)s->d_lgrid;
+        a.lg_start = (const int32_t*)s->d_lg_start;
+        a.lg_faces = (const int32_t*)s->d_lg_faces;
+        a.lg_d2 = (const float*)s->d_lg_d2;
+    }
+    bind_scene(H, a, s->view);
+    // what only the device reads; the faces stay for the camera's face bins (one mesh) and
+    // the hierarchy bounds
+    std::vector<uint32_t>().swap(H.texels);
+    std::vector<float>().swap(H.lut255);
+    std::vector<DTriN>().swap(H.trins);
+    std::vector<DFaceBox>().swap(H.fboxes);
+    std::vector<DLeaf>().swap(H.leaves);
+    std::vector<int32_t>().swap(H.tri_orig);
+    if (H.n_mesh != 1 && H.nodes.empty()) std::vector<DTri>().swap(H.tris);
     {  // the first launch of any of the library's kernels loads its code object (~1 ms):
        // once per process, here rather than in the first camera upload
         static std::once_flag loaded;
@@ -3194,260 +3479,91 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
     int rc = convert_camera(c, k);
     if (rc) return rc;
     free_camera(s);
-    const size_t nsamp = (size_t)c->n_dof * c->n_aa;
-    const std::vector<float> times = camera_times(c);
-    const auto mm = std::minmax_element(times.begin(), times.end());
-    const double omax = camera_origin_bound(c);
+    const HostScene& H = s->H;
     k.S = s->view;
     slog.mark("convert");
     // what depends on the frame's time range only: computed again when it changes
-    const bool dsg_off = !opt_on(OPT_DSGRID);  // every shadow ray tests every object
-    const double dsg_min = opt(OPT_DSGRID_MIN);  // (dir_shadow_grids reads it)
-    if (!s->tr_valid || s->tr_lo != *mm.first || s->tr_hi != *mm.second || s->tr_dsg_off != dsg_off ||
-        s->tr_dsg_min != dsg_min) {
-        s->tr_bounds.clear();
-        if (!s->h_nodes.empty())  // hierarchy bounds over the frame's motion-time range
-            s->tr_bounds = compute_bounds(s->h_nodes, s->h_objs, s->h_tris, *mm.first, *mm.second);
-        std::vector<DSCell> cells;
-        std::vector<DSRect> rects;
-        size_t ncells = 0;
-        s->tr_grids.clear();
-        s->tr_dsg_off = dsg_off;
-        s->tr_dsg_min = dsg_min;
-        s->tr_grids_on = !dsg_off && dir_shadow_grids(s->h_bins, s->tr_bounds, *mm.first, *mm.second, s->tr_grids,
-                                                      cells, &rects, &ncells);
+    std::vector<float> times = camera_times(c);
+    const auto mm = std::minmax_element(times.begin(), times.end());
+    const float tlo = *mm.first, thi = *mm.second;
+    TimeTables& tr = s->tr;
+    if (!tr.holds(tlo, thi)) {
+        tr.build(H, tlo, thi, true);
         (void)hipDeviceSynchronize();  // (frames of the previous camera may still read the cells)
-        (void)hipFree(s->d_dsg_cells);
-        s->d_dsg_cells = nullptr;
-        if (s->tr_grids_on) {  // the cells, then the rectangles k_dsg_fill reads
-            const size_t n = sizeof(DSCell) * ncells, nr = sizeof(DSRect) * rects.size();
-            RTX_HIP(hipMalloc(&s->d_dsg_cells, n + std::max<size_t>(nr, 16)));
+        (void)hipFree(tr.d_cells);
+        tr.d_cells = nullptr;
+        if (tr.grids_on) {  // the cells, then the rectangles k_dsg_fill reads
+            const size_t n = sizeof(DSCell) * tr.ncells, nr = sizeof(DSRect) * tr.rects.size();
+            RTX_HIP(hipMalloc(&tr.d_cells, n + std::max<size_t>(nr, 16)));
             if (nr) {
                 if ((rc = pinned_reserve(s, nr))) return rc;
-                memcpy(s->h_cam, rects.data(), nr);
-                if ((rc = pinned_upload(s, (char*)s->d_dsg_cells + n, nr))) return rc;
+                memcpy(s->h_cam, tr.rects.data(), nr);
+                if ((rc = pinned_upload(s, (char*)tr.d_cells + n, nr))) return rc;
             }
-            hipLaunchKernelGGL(k_dsg_fill, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, nullptr,
-                               (const DSRect*)((char*)s->d_dsg_cells + n), (int32_t)rects.size(),
-                               (DSCell*)s->d_dsg_cells, (int64_t)ncells, s->tr_grids.empty() ? 0 : kDsgG);
+            hipLaunchKernelGGL(k_dsg_fill, dim3((unsigned)((tr.ncells + 255) / 256)), dim3(256), 0, nullptr,
+                               (const DSRect*)((char*)tr.d_cells + n), (int32_t)tr.rects.size(), (DSCell*)tr.d_cells,
+                               (int64_t)tr.ncells, tr.grids.empty() ? 0 : kDsgG);
             RTX_HIP(hipGetLastError());
             RTX_HIP(hipStreamSynchronize(nullptr));
         }
-        s->tr_valid = true;
-        s->tr_lo = *mm.first;
-        s->tr_hi = *mm.second;
+        std::vector<DSRect>().swap(tr.rects);
+        tr.valid = true;
     }
     slog.mark("time-range grids");
-    CamStage st;
-    const size_t o_xs = st.put(c->xs, sizeof(float) * c->ncols), o_ys = st.put(c->ys, sizeof(float) * c->height);
-    const size_t o_dof = st.put(c->dof_origins, sizeof(float) * 3 * c->n_dof);
-    const size_t o_aa = st.put(c->aa_origins, sizeof(float) * 3 * nsamp);
-    const size_t o_times = st.put(times);
-    size_t o_noise = 0, o_bounds = 0, o_pself = 0, o_dsg = 0, o_bstart = 0, o_bfaces = 0, o_bz = 0, o_bmask = 0;
-    size_t o_tperm = 0, o_ttime = 0;
-    const bool replay = c->jitter == RTX_JITTER_REPLAY;
-    if (replay) o_noise = st.put(c->noise, sizeof(float) * 3 * (size_t)c->ncols * c->height * nsamp);
-    slog.mark("tables", st.size());
-    // (put() keeps pointers: every staged table lives until the upload)
-    std::vector<DBox> boxes;
-    std::vector<float> pself_lim;
-    std::vector<DSGrid> grids;
-    std::vector<int32_t> ident;
-    if (!s->h_nodes.empty()) {
-        boxes = split_bounds(s->tr_bounds);
-        o_bounds = st.put(boxes);
-    }
-    // self tests of planes (option self_skip 0: none). Scenes with secondary rays get none:
-    // MirrorRefraction measured 1.4 % slower with them (most of its shadow rays leave
-    // deeper levels, which pay the check and never skip), TSP 3 % and TM 2 % faster
-    // (profiles/r04/plane_self/)
-    const bool pself = opt_on(OPT_SELF_SKIP) && s->view.n_plane > 0 && !s->h_bins.lights.empty() && !s->has_secondary;
-    if (pself) {
-        pself_lim = plane_self_limits(s->h_bins, omax);
-        o_pself = st.put(pself_lim);
-    }
-    if (s->tr_grids_on) {  // the grid headers with this camera's self-test marks
-        grids = s->tr_grids;
-        dir_self_boxes(s->h_bins, grids, omax);
-        o_dsg = st.put(grids);
-    }
-    slog.mark("self tests", st.size());
-    std::vector<int32_t> bstart, bfaces;
-    std::vector<float> bz;
-    std::vector<uint32_t> bmask, brmask;
-    int32_t bins_x = 0, mesh_bins = 0, dev_pairs = 0;
-    bool dev_faces = false;  // the mesh's face bins are built on the device (rtx_bins.hip)
-    const bool bins = opt_on(OPT_BINS) &&
-                      primary_bins(s->h_bins, c, s->tr_bounds, bstart, bfaces, bz, bmask, brmask, bins_x, mesh_bins,
-                                   opt_on(OPT_DEV_BINS) ? &dev_faces : nullptr);
-    if (bins && dev_faces) {
-        if ((rc = mesh_bins_dev1(s, c, bins_x, bstart, &dev_pairs, &mesh_bins, slog))) return rc;
-        dev_faces = dev_pairs > 0;
-        slog.mark("face bins: counts read back");
-    }
-    if (bins) {
-        if (bfaces.empty() && !dev_faces) { bfaces.push_back(0); bz.push_back(0.0f); }
-        bmask.insert(bmask.end(), brmask.begin(), brmask.end());  // [object masks | root masks]
-        o_bstart = st.put(bstart);
-        if (!dev_faces) {  // (the device-filled lists go last: below)
-            o_bfaces = st.put(bfaces);
-            o_bz = st.put(bz);
-        }
-        o_bmask = st.put(bmask);
-    }
-    std::vector<int32_t> bheavy;
-    std::vector<int2> hitems;
-    size_t o_bheavy = 0, o_hitems = 0, o_mhits = 0;
-    const bool heavy = bins && mesh_bins && !s->has_ext && opt_on(OPT_HEAVY_TILES) && heavy_chunks(bstart, bheavy, hitems);
-    if (heavy) {
-        o_bheavy = st.put(bheavy);
-        o_hitems = st.put(hitems);
-        // (o_mhits: below, device-filled)
-    }
-    // shadow bins (option shadow_bins 0: none): flat scenes of primary and shadow rays. Scenes
-    // with secondary rays get none, as with the planes' self tests: most of their shadow rays
-    // leave deeper levels, which would pay the check and never skip
-    SbScene sbs;
-    size_t o_sbs = 0, o_bshadow = 0;
-    const bool sbins = bins && opt_on(OPT_SHADOW_BINS) && (!s->has_secondary || opt(OPT_SHADOW_BINS) >= 2) && !s->has_mesh && !s->has_ext &&
-                       shadow_bins_scene(s->h_bins, c, bins_x, 1.0, sbs);
-    if (sbins) o_sbs = st.put(&sbs, sizeof(sbs));  // (o_bshadow: below, device-filled)
-    slog.mark("bins", st.size());
-    // the measured tile schedule (tile_schedule): identity order until measured
-    const bool tsched = tile_sched_enabled() && !s->has_ext && (s->has_secondary || s->has_mesh);
-    int64_t tiles = 0;
-    if (tsched) {
-        const int64_t wpb = kBlock<false> / 64;
-        tiles = (int64_t)((c->ncols + 7) / 8) * ((c->height + 7) / 8);
-        const int64_t nw = (tiles + wpb - 1) / wpb * wpb;
-        ident.resize((size_t)nw);
-        std::iota(ident.begin(), ident.end(), 0);
-        o_tperm = st.put(ident);
-        // (o_ttime: below, device-filled)
-    }
-    const size_t o_kp = st.put(nullptr, sizeof(KParams));
-    // the segments the device fills, last: the host stages (and uploads) only what precedes
-    // them -- the face lists of device bins, the heavy tiles' per-frame hits (the chunk pass
-    // writes them) and the tile times (a measured frame writes them before they are read)
-    const size_t host_bytes = st.size();
-    if (dev_faces) {
-        o_bfaces = st.put(nullptr, sizeof(int32_t) * dev_pairs, true);
-        o_bz = st.put(nullptr, sizeof(float) * dev_pairs, true);
-    }
-    if (heavy) o_mhits = st.put(nullptr, sizeof(uint2) * 64 * hitems.size(), true);
-    if (sbins) o_bshadow = st.put(nullptr, sizeof(uint32_t) * (size_t)sbs.bins_x * sbs.bins_y * sbs.NL, true);
-    if (tsched) {
-        const int64_t nw = (tiles + kBlock<false> / 64 - 1) / (kBlock<false> / 64) * (kBlock<false> / 64);
-        o_ttime = st.put(nullptr, sizeof(uint32_t) * nw, true);
-    }
-    slog.mark("tile schedule", st.size());
+    CamTables T;
+    auto dev1 = [&](int32_t bins_x, std::vector<int32_t>& start, int32_t* npairs, int32_t* mesh_bins) {
+        return mesh_bins_dev1(s, c, bins_x, start, npairs, mesh_bins, slog);
+    };
+    if ((rc = T.build(H, c, std::move(times), tr, std::ref(dev1), slog))) return rc;
     // one device buffer for all of it, reused while large enough; its old contents may still
     // be read by frames of the previous camera
     (void)hipDeviceSynchronize();
-    if (s->cam_cap < st.size()) {
+    if (s->cam_cap < T.st.size()) {
         (void)hipFree(s->d_cam);
         s->d_cam = nullptr;
         s->cam_cap = 0;
-        const size_t cap = st.size() + st.size() / 4;
+        const size_t cap = T.st.size() + T.st.size() / 4;
         RTX_HIP(hipMalloc((void**)&s->d_cam, cap));
         s->cam_cap = cap;
     }
     char* const D = s->d_cam;
     slog.mark("sync+alloc");
-    k.xs = (cptr<float>)(D + o_xs);
-    k.ys = (cptr<float>)(D + o_ys);
-    k.dof_o = (cptr<float>)(D + o_dof);
-    k.aa_o = (cptr<float>)(D + o_aa);
-    k.times = (cptr<float>)(D + o_times);
-    k.noise = replay ? (cptr<float>)(D + o_noise) : nullptr;
-    if (!s->h_nodes.empty()) bind_boxes(k.S, (const DBox*)(D + o_bounds), s->h_nodes.size());
-    if (pself) k.S.plane_self = (cptr<float>)(D + o_pself);
-    if (s->tr_grids_on) {
-        k.S.dsgrid = (cptr<DSGrid>)(D + o_dsg);
-        k.S.dsg_cells = (cptr<DSCell>)s->d_dsg_cells;
-        k.S.dsg_on = 1;
-    }
-    if (bins) {
-        k.S.bin_objmask = (cptr<uint32_t>)(D + o_bmask);
-        k.S.bin_rootmask = (cptr<uint32_t>)(D + o_bmask) + brmask.size();
-        k.S.mesh_bins = mesh_bins;
-        k.S.bin_start = (cptr<int32_t>)(D + o_bstart);
-        k.S.bin_faces = (cptr<int32_t>)(D + o_bfaces);
-        k.S.bin_zmin = (cptr<float>)(D + o_bz);
-        k.S.bins_x = bins_x;
-        k.S.bins_on = 1;
-    }
-    if (sbins) k.S.bin_shadow = (cptr<uint32_t>)(D + o_bshadow);
-    s->heavy_n = 0;
-    s->d_heavy_items = nullptr;
-    s->d_mesh_hits = nullptr;
-    if (heavy) {
-        k.S.bin_heavy = (cptr<int32_t>)(D + o_bheavy);
-        k.S.mesh_hits = reinterpret_cast<const uint2*>(D + o_mhits);
-        s->d_heavy_items = reinterpret_cast<const int2*>(D + o_hitems);
-        s->d_mesh_hits = reinterpret_cast<uint2*>(D + o_mhits);
-        s->heavy_n = (int32_t)hitems.size();
+    T.bind(k, D, H, c, tr);
+    s->heavy_n = T.heavy ? (int32_t)T.hitems.size() : 0;
+    s->d_heavy_items = T.heavy ? reinterpret_cast<const int2*>(D + T.o_hitems) : nullptr;
+    s->d_mesh_hits = T.heavy ? reinterpret_cast<uint2*>(D + T.o_mhits) : nullptr;
+    if (T.tsched) {
+        s->d_tile_perm = D + T.o_tperm;
+        s->d_tile_time = D + T.o_ttime;
+        s->tile_sched = 1;
     }
 #if defined(RTX_WAVE_LOG)  // tools/wave_timeline.py builds only
     if (const char* e = getenv("RTX_WAVE_LOG_PTR"))
         k.wave_log = reinterpret_cast<unsigned long long*>((uintptr_t)strtoull(e, nullptr, 0));
 #endif
-    // one sample, no jitter, static scene: every primary ray starts at aa_o[0], so its
-    // origin-only plane and sphere terms are per-frame constants (closest_hit's fp32
-    // operations, here once; RTX_PRIM_ORIGIN kernels read them)
-    // (flat primary + shadow scenes: TwoSpheresPlane 24.09 -> 23.59 us, TorusMesh -0.6 %;
-    // MirrorRefraction measured 1 % slower with them, profiles/r04/prim_origin/)
-    if (c->n_dof == 1 && c->n_aa == 1 && c->jitter == RTX_JITTER_OFF && !s->traits.any_speed && !s->has_ext &&
-        !s->has_secondary && s->view.n_plane <= 4 && s->view.n_sphere <= 16 && prim_origin_enabled()) {
-        const f3 o = mk(c->aa_origins[0], c->aa_origins[1], c->aa_origins[2]);
-        int oi = 0;
-        for (int q = 0; q < s->view.n_plane; ++q, ++oi) {
-            const DObj& ob = s->h_bins.objs[oi];
-            k.po_pnum[q] = dot(sub(moved(ob, ob.a, 0.0f), o), ld3(ob.b));
-        }
-        for (int q = 0; q < s->view.n_sphere; ++q, ++oi) {
-            const DObj& ob = s->h_bins.objs[oi];
-            const f3 oc = sub(o, moved(ob, ob.a, 0.0f));
-            k.po_soc[q][0] = oc.x; k.po_soc[q][1] = oc.y; k.po_soc[q][2] = oc.z;
-            k.po_sq[q] = dot(oc, oc);
-        }
-        k.po_valid = 1;
-    }
-    if (tsched) {
-        k.tile_perm = (cptr<int32_t>)(D + o_tperm);
-        k.tile_time = reinterpret_cast<unsigned int*>(D + o_ttime);
-        k.tile_n = (int32_t)tiles;
-        s->d_tile_perm = D + o_tperm;
-        s->d_tile_time = D + o_ttime;
-        s->tile_sched = 1;
-    }
-    // the camera block's copies of the first DOF and AA origins (rtx_kernels.h KParams),
-    // refreshed with the tables on every upload
-    set3(k.dof0, c->dof_origins);
-    set3(k.aa0, c->aa_origins);
-    if ((rc = pinned_reserve(s, host_bytes))) return rc;
-    st.write(s->h_cam);
-    memcpy(s->h_cam + o_kp, &k, sizeof(KParams));
-    for (const auto& r : st.runs())  // (the segments the device fills are not uploaded)
+    if ((rc = pinned_reserve(s, T.host_bytes))) return rc;
+    T.st.write(s->h_cam);
+    memcpy(s->h_cam + T.o_kp, &k, sizeof(KParams));
+    for (const auto& r : T.st.runs())  // (the segments the device fills are not uploaded)
         if ((rc = pinned_upload(s, D + r.first, r.second - r.first, r.first))) return rc;
     slog.mark("upload");
-    if (sbins) {  // the shadow bins, from the tables just uploaded (one thread per bin)
-        const int32_t nbin = sbs.bins_x * sbs.bins_y;
+    if (T.sbins) {  // the shadow bins, from the tables just uploaded (one thread per bin)
+        const int32_t nbin = T.sbs.bins_x * T.sbs.bins_y;
         hipLaunchKernelGGL(k_shadow_bins, dim3((unsigned)((nbin + 63) / 64)), dim3(64), 0, nullptr,
-                           reinterpret_cast<const SbScene*>(D + o_sbs), reinterpret_cast<const float*>(D + o_xs),
-                           reinterpret_cast<const float*>(D + o_ys), reinterpret_cast<const uint32_t*>(D + o_bmask),
-                           reinterpret_cast<uint32_t*>(D + o_bshadow));
+                           reinterpret_cast<const SbScene*>(D + T.o_sbs), reinterpret_cast<const float*>(D + T.o_xs),
+                           reinterpret_cast<const float*>(D + T.o_ys), reinterpret_cast<const uint32_t*>(D + T.o_bmask),
+                           reinterpret_cast<uint32_t*>(D + T.o_bshadow));
         RTX_HIP(hipGetLastError());
         RTX_HIP(hipStreamSynchronize(nullptr));
         slog.mark("shadow bins (device)");
     }
-    if (dev_faces) {
-        if ((rc = mesh_bins_dev2(s, bins_x, (int32_t)(bstart.size() - 1), dev_pairs, reinterpret_cast<int32_t*>(D + o_bfaces),
-                                 reinterpret_cast<float*>(D + o_bz))))
+    if (T.dev_faces) {
+        if ((rc = mesh_bins_dev2(s, T.bins_x, (int32_t)(T.bstart.size() - 1), T.dev_pairs,
+                                 reinterpret_cast<int32_t*>(D + T.o_bfaces), reinterpret_cast<float*>(D + T.o_bz))))
             return rc;
         slog.mark("device face bins (stage 2)");
     }
-    s->d_kp = reinterpret_cast<KParams*>(D + o_kp);
+    s->d_kp = reinterpret_cast<KParams*>(D + T.o_kp);
     s->kp = k;
     s->cam_set = true;
     return RTX_OK;
@@ -3796,12 +3912,12 @@ int render_split(rtx_scene* s, Launch L, const KParams* kp, size_t hbytes, hipSt
             r.block = B;
             // option jit_csg 2 / 3: the camera's boxes / and the object records as literals too
             const int bake = opt(OPT_JIT_CSG) >= 3.0 ? 3 : opt(OPT_JIT_CSG) >= 2.0 ? 2 : 0;
-            const bool can = !s->csg_tables.empty() && s->tr_valid && s->tr_bounds.size() == s->h_nodes.size();
+            const bool can = !s->csg_tables.empty() && s->tr.valid && s->tr.bounds.size() == s->H.nodes.size();
             r.lds = pass < 2 && (((int)opt(OPT_CSG_RAYS) >> pass) & 1) == 0;
             std::vector<std::string> fixed;
             jit_fixed_opts(s->view, s->kp, s->traits, false, fixed);
             jit_split_kernel(s->device,
-                             bake && can ? s->csg_tables + jit_csg_baked(s->tr_bounds, s->h_objs, bake) : s->csg_tables,
+                             bake && can ? s->csg_tables + jit_csg_baked(s->tr.bounds, s->H.objs, bake) : s->csg_tables,
                              s->has_mesh, s->has_secondary, cnt, (sel & 1) != 0, pass, !r.lds, fixed, r);
             if (r.pending && !opt_on(OPT_JIT_ASYNC) && !capturing) jit_poll(r, true);
             r.done = true;
@@ -4026,11 +4142,11 @@ namespace {
 // The scene view for the motion times [tlo, thi] (hierarchy bounds uploaded in stream order).
 int view_at(rtx_scene* s, float tlo, float thi, hipStream_t stream, SceneView& v) {
     v = s->view;
-    if (s->h_nodes.empty()) return RTX_OK;
-    s->h_bounds_abi = split_bounds(compute_bounds(s->h_nodes, s->h_objs, s->h_tris, tlo, thi));
+    if (s->H.nodes.empty()) return RTX_OK;
+    s->h_bounds_abi = split_bounds(compute_bounds(s->H.nodes, s->H.objs, s->H.tris, tlo, thi));
     RTX_HIP(hipMemcpyAsync(s->d_bounds_abi, s->h_bounds_abi.data(), sizeof(DBox) * s->h_bounds_abi.size(),
                            hipMemcpyHostToDevice, stream));
-    bind_boxes(v, (const DBox*)s->d_bounds_abi, s->h_nodes.size());
+    bind_boxes(v, (const DBox*)s->d_bounds_abi, s->H.nodes.size());
     return RTX_OK;
 }
 }  // namespace

@@ -25,99 +25,99 @@ hipError_t mesh_bins_stage2(MeshBinsDev&, int32_t, int32_t, int32_t, int32_t, vo
 #include <chrono>
 
 namespace {
-void bind_view(const HostScene& H, SceneView& v) {
-    v.objs = (cptr<DObj>)H.objs.data();
-    v.tris = (cptr<DTri>)H.tris.data();
-    v.trins = (cptr<DTriN>)H.trins.data();
-    v.fboxes = (cptr<DFaceBox>)H.fboxes.data();
-    v.mats = (cptr<DMat>)H.mats.data();
-    v.lights = (cptr<DLight>)H.lights.data();
-    v.leaves = (cptr<DLeaf>)H.leaves.data();
-    v.tri_orig = (cptr<int32_t>)H.tri_orig.data();
-    v.n_objs = H.n_objs;
-    v.n_lights = H.n_lights;
-    v.n_plane = H.n_plane; v.n_sphere = H.n_sphere; v.n_box = H.n_box; v.n_mesh = H.n_mesh;
-    v.pow_bits = H.pow_bits;
-    std::memcpy(v.ambient, H.ambient, sizeof(v.ambient));
-    v.texels = (cptr<uint32_t>)H.texels.data();
-    v.lut255 = (cptr<float>)H.lut255.data();
-    v.n_nodes = (int32_t)H.nodes.size();
-    v.hlevels = H.hlevels;
-}
-
-// The device forms of the hierarchy records, as rtx_scene_create / rtx_camera_set upload
-// them: split nodes and the boxes for the time range [tlo, thi].
-struct Nodes {
+// A scene as rtx_scene_create sets it up, by the library's own builders (split_nodes,
+// LightGrids, bind_scene), with the host arrays bound in place of device buffers.
+struct EmuScene {
+    HostScene H;
     std::vector<DNodeHot> hot;
     std::vector<DNodeMat> mat;
-    std::vector<DBound> bounds;
+    LightGrids lg;
     std::vector<DBox> boxes;
-    void bind(const HostScene& H, SceneView& v, float tlo, float thi) {
+    SceneView view{};
+    int init(const rtx_scene_desc* sd, bool light_grids = true) {
+        if (int rc = convert_scene(sd, H)) return rc;
         split_nodes(H.nodes, hot, mat);
-        bounds = compute_bounds(H.nodes, H.objs, H.tris, tlo, thi);
-        boxes = split_bounds(bounds);
-        v.nodes = (cptr<DNodeHot>)hot.data();
-        v.nmat = (cptr<DNodeMat>)mat.data();
-        bind_boxes(v, boxes.data(), H.nodes.size());
-    }
-};
-
-// The light grids rtx_scene_create builds (RTX_LGRID=0: none), bound to the view.
-struct Grids {
-    std::vector<DLGrid> grids;
-    std::vector<int32_t> start, faces;
-    std::vector<float> d2;
-    void bind(const HostScene& H, SceneView& v) {
-        if (!opt_on(OPT_LGRID) || !light_grids(H, grids, start, faces, d2)) return;
-        if (faces.empty()) { faces.push_back(0); d2.push_back(0.0f); }
-        v.lgrid = (cptr<DLGrid>)grids.data();
-        v.lg_start = (cptr<int32_t>)start.data();
-        v.lg_faces = (cptr<int32_t>)faces.data();
-        v.lg_d2 = (cptr<float>)d2.data();
-        v.lgrid_on = 1;
-    }
-};
-
-// The directional lights' shadow grids rtx_camera_set builds for the motion-time range
-// [tlo, thi] (RTX_DSGRID=0: none).
-struct DirGrids {
-    std::vector<DSGrid> grids;
-    std::vector<DSCell> cells;
-    std::vector<float> pself;
-    void bind(const HostScene& H, SceneView& v, float tlo, float thi, double omax = INFINITY) {
-        // the planes' self tests, as rtx_camera_set
-        if (opt_on(OPT_SELF_SKIP) && H.n_plane > 0 && !H.lights.empty()) {
-            pself = plane_self_limits(H, omax);
-            v.plane_self = (cptr<float>)pself.data();
+        SceneArrays a;
+        a.objs = H.objs.data(); a.tris = H.tris.data(); a.trins = H.trins.data(); a.fboxes = H.fboxes.data();
+        a.mats = H.mats.data(); a.lights = H.lights.data(); a.leaves = H.leaves.data(); a.tri_orig = H.tri_orig.data();
+        a.texels = H.texels.data(); a.lut255 = H.lut255.data(); a.nodes = hot.data(); a.nmat = mat.data();
+        if (light_grids && lg.build(H)) {
+            a.lgrid = lg.grids.data(); a.lg_start = lg.start.data(); a.lg_faces = lg.faces.data(); a.lg_d2 = lg.d2.data();
         }
-        if (!opt_on(OPT_DSGRID)) return;
-        std::vector<DBound> nb;
-        if (!H.nodes.empty()) nb = compute_bounds(H.nodes, H.objs, H.tris, tlo, thi);
-        if (!dir_shadow_grids(H, nb, tlo, thi, grids, cells)) return;
-        dir_self_boxes(H, grids, omax);
-        v.dsgrid = (cptr<DSGrid>)grids.data();
-        v.dsg_cells = (cptr<DSCell>)cells.data();
-        v.dsg_on = 1;
+        bind_scene(H, a, view);
+        return RTX_OK;
+    }
+    // the view with the hierarchy bounds of motion time t (rtx_api.hip view_at)
+    SceneView at(float t) {
+        SceneView v = view;
+        boxes = split_bounds(compute_bounds(H.nodes, H.objs, H.tris, t, t));
+        bind_boxes(v, boxes.data(), H.nodes.size());
+        return v;
     }
 };
 
-// The heavy tiles' chunks (rtx_api.hip heavy_chunks, rtx_kernels.h mesh_chunk), as the
-// k_mesh_chunks pass computes them before each frame, for every chunk and pixel.
-struct Heavy {
-    std::vector<int32_t> bheavy;
-    std::vector<int2> items;
-    std::vector<uint2> hits;
-    void bind(const HostScene& H, KParams& k, const std::vector<int32_t>& bstart) {
-        if (!k.S.bins_on || !k.S.mesh_bins || H.has_ext || !heavy_chunks(bstart, bheavy, items)) return;
-        hits.resize(items.size() * 64);
-        k.S.bin_heavy = (cptr<int32_t>)bheavy.data();
+// A camera as rtx_camera_set sets it up, by the same TimeTables and CamTables, in a host
+// buffer. What the library's device passes fill, the device source fills here: the shadow
+// grids' cells (dir_shadow_grids), the face bins (primary_bins), the heavy tiles' hits
+// (mesh_chunk, every chunk and pixel as k_mesh_chunks before each frame) and the shadow
+// bins (shadow_bins). fill = false: the tables and their binding only, for the entry points
+// that report a table and run no kernel code (nor the jit spec, which reads no table).
+struct EmuCam : EmuScene {
+    KParams k;
+    TimeTables tr;
+    CamTables T;
+    std::vector<char> buf;
+    int init(const rtx_scene_desc* sd, const rtx_camera_desc* cd, bool fill = true) {
+        int rc = EmuScene::init(sd);
+        if (rc) return rc;
+        if ((rc = convert_camera(cd, k))) return rc;
+        k.S = view;
+        std::vector<float> times = camera_times(cd);
+        const auto mm = std::minmax_element(times.begin(), times.end());
+        tr.build(H, *mm.first, *mm.second, false);
+        SetupLog slog(nullptr);  // (silent)
+        if ((rc = T.build(H, cd, std::move(times), tr, nullptr, slog))) return rc;
+        buf.assign(T.st.size(), 0);
+        T.st.write(buf.data());
+        T.bind(k, buf.data(), H, cd, tr);
+        if (!fill) return RTX_OK;
+        if (T.sbins) {
+            std::vector<uint32_t> m;
+            if (!shadow_bins(H, cd, T.bmask, T.bins_x, m)) return fail(RTX_ERR_INVALID, "hostemu: shadow bins");
+            memcpy(buf.data() + T.o_bshadow, m.data(), sizeof(uint32_t) * m.size());
+        }
+        if (T.heavy) {
+            uint2* hits = reinterpret_cast<uint2*>(buf.data() + T.o_mhits);
 #pragma omp parallel for schedule(dynamic, 4)
-        for (int64_t w = 0; w < (int64_t)items.size(); ++w)
-            for (int lane = 0; lane < 64; ++lane)
-                hits[(size_t)w * 64 + lane] = mesh_chunk(k, items[(size_t)w].x, items[(size_t)w].y, lane);
-        k.S.mesh_hits = hits.data();
+            for (int64_t w = 0; w < (int64_t)T.hitems.size(); ++w)
+                for (int lane = 0; lane < 64; ++lane)
+                    hits[(size_t)w * 64 + lane] = mesh_chunk(k, T.hitems[(size_t)w].x, T.hitems[(size_t)w].y, lane);
+        }
+        return RTX_OK;
     }
 };
+
+// "name\n" + one option per line + "\n" + the source, into out (at most cap bytes,
+// NUL-terminated); returns the text's length.
+int64_t spec_text(const JitSpec& sp, char* out, int64_t cap) {
+    std::string s = sp.name + "\n";
+    for (const auto& o : sp.opts) s += o + "\n";
+    s += "\n" + sp.src;
+    if (out && cap > 0) {
+        const size_t n = std::min((size_t)cap - 1, s.size());
+        memcpy(out, s.data(), n);
+        out[n] = '\0';
+    }
+    return (int64_t)s.size();
+}
+
+// One pixel's tallies into a counter block.
+void add_tally(uint64_t* loc, const Tally& tl) {
+    for (int q = 0; q < kMaxDepth; ++q) loc[q] += tl.cast[q];
+    loc[RTX_CNT_SHADOW] += tl.shadow;
+    loc[RTX_CNT_SHADE] += tl.shade;
+    loc[RTX_CNT_TRI] += tl.tri;
+}
 
 // Dispatch over the kernel template flags, as rtx_render's launch switch does.
 template <bool MESH, bool SEC, bool X>
@@ -143,50 +143,12 @@ void pixel_any(const HostScene& H, const KParams& k, float* fb, int32_t row0, in
         case 7: pixel_jit<true, true, true>(k, fb, row0, rr, cc, tl, fs, hs, jit, bin); break;
     }
 }
-}  // namespace
 
-extern "C" int rtx_hostemu_render(const rtx_scene_desc* sd, const rtx_camera_desc* cd, int32_t row0, int32_t nrows,
-                                  float* fb, uint64_t* counters, int threads) {
-    HostScene H;
-    int rc = convert_scene(sd, H);
-    if (rc) return rc;
-    KParams k;
-    if ((rc = convert_camera(cd, k))) return rc;
-    if (row0 < 0 || nrows < 0 || row0 + nrows > cd->height) return fail(RTX_ERR_INVALID, "bad rows");
-    bind_view(H, k.S);
-    Grids lg;
-    lg.bind(H, k.S);
-    std::vector<float> times(cd->n_times);
-    for (int i = 0; i < cd->n_times; ++i) times[i] = (float)cd->times[i];
-    const auto mm = std::minmax_element(times.begin(), times.end());
-    Nodes nv;
-    nv.bind(H, k.S, *mm.first, *mm.second);
-    DirGrids dg;
-    dg.bind(H, k.S, *mm.first, *mm.second, camera_origin_bound(cd));
-    std::vector<int32_t> bstart, bfaces;
-    std::vector<float> bz;
-    std::vector<uint32_t> bmask, brmask;
-    int32_t bins_x = 0, mesh_bins = 0;
-    if (opt_on(OPT_BINS) && primary_bins(H, cd, nv.bounds, bstart, bfaces, bz, bmask, brmask, bins_x, mesh_bins)) {
-        if (bfaces.empty()) { bfaces.push_back(0); bz.push_back(0.0f); }
-        k.S.bin_start = (cptr<int32_t>)bstart.data();
-        k.S.bin_faces = (cptr<int32_t>)bfaces.data();
-        k.S.bin_zmin = (cptr<float>)bz.data();
-        k.S.bin_objmask = (cptr<uint32_t>)bmask.data();
-        k.S.bin_rootmask = (cptr<uint32_t>)brmask.data();
-        k.S.mesh_bins = mesh_bins;
-        k.S.bins_x = bins_x;
-        k.S.bins_on = 1;
-    }
-    std::vector<float> noise;
-    const size_t nsamp = (size_t)cd->n_dof * cd->n_aa;
-    if (cd->jitter == RTX_JITTER_REPLAY) noise.assign(cd->noise, cd->noise + 3 * (size_t)cd->ncols * cd->height * nsamp);
-    k.xs = (cptr<float>)cd->xs; k.ys = (cptr<float>)cd->ys; k.dof_o = (cptr<float>)cd->dof_origins;
-    k.aa_o = (cptr<float>)cd->aa_origins; k.times = (cptr<float>)times.data(); k.noise = (cptr<float>)noise.data();
-    Heavy hv;
-    hv.bind(H, k, bstart);
+// Image rows [row0, row0 + nrows) of the camera, every pixel through render_pixel; tot
+// (if given) gets the tallies.
+void render_block(const EmuCam& E, int32_t row0, int32_t nrows, float* fb, uint64_t* tot, int threads) {
+    const KParams& k = E.k;
     const int64_t npix = (int64_t)nrows * k.ncols;
-    uint64_t tot[RTX_COUNTERS] = {};
 #pragma omp parallel num_threads(threads > 0 ? threads : 1)
     {
         uint64_t loc[RTX_COUNTERS] = {};
@@ -198,15 +160,24 @@ extern "C" int rtx_hostemu_render(const rtx_scene_desc* sd, const rtx_camera_des
             const FrameStack fs{frames, 1};
             const HStack hs{hst, 1};
             const int32_t rr = (int32_t)(p / k.ncols), cc = (int32_t)(p % k.ncols);
-            pixel_any(H, k, fb, row0, rr, cc, tl, fs, hs, k.jitter != RTX_JITTER_OFF, row0 + (rr & ~7));
-            for (int q = 0; q < kMaxDepth; ++q) loc[q] += tl.cast[q];
-            loc[RTX_CNT_SHADOW] += tl.shadow;
-            loc[RTX_CNT_SHADE] += tl.shade;
-            loc[RTX_CNT_TRI] += tl.tri;
+            pixel_any(E.H, k, fb, row0, rr, cc, tl, fs, hs, k.jitter != RTX_JITTER_OFF, row0 + (rr & ~7));
+            add_tally(loc, tl);
         }
+        if (tot) {
 #pragma omp critical
-        for (int q = 0; q < RTX_COUNTERS; ++q) tot[q] += loc[q];
+            for (int q = 0; q < RTX_COUNTERS; ++q) tot[q] += loc[q];
+        }
     }
+}
+}  // namespace
+
+extern "C" int rtx_hostemu_render(const rtx_scene_desc* sd, const rtx_camera_desc* cd, int32_t row0, int32_t nrows,
+                                  float* fb, uint64_t* counters, int threads) {
+    EmuCam E;
+    if (int rc = E.init(sd, cd)) return rc;
+    if (row0 < 0 || nrows < 0 || row0 + nrows > cd->height) return fail(RTX_ERR_INVALID, "bad rows");
+    uint64_t tot[RTX_COUNTERS] = {};
+    render_block(E, row0, nrows, fb, tot, threads);
     if (counters)
         for (int q = 0; q < RTX_COUNTERS; ++q) counters[q] = tot[q];
     return RTX_OK;
@@ -216,45 +187,11 @@ extern "C" int rtx_hostemu_render(const rtx_scene_desc* sd, const rtx_camera_des
 // frame (rtx_render's contiguous block or rtx_render_groups' interleaved 8-row groups).
 extern "C" int rtx_hostemu_render_rows(const rtx_scene_desc* sd, const rtx_camera_desc* cd, const int32_t* rows,
                                        int32_t nrows, float* fb, int threads) {
-    HostScene H;
-    int rc = convert_scene(sd, H);
-    if (rc) return rc;
-    KParams k;
-    if ((rc = convert_camera(cd, k))) return rc;
+    EmuCam E;
+    if (int rc = E.init(sd, cd)) return rc;
     for (int32_t r = 0; r < nrows; ++r)
         if (rows[r] < 0 || rows[r] >= cd->height) return fail(RTX_ERR_INVALID, "bad rows");
-    bind_view(H, k.S);
-    Grids lg;
-    lg.bind(H, k.S);
-    std::vector<float> times(cd->n_times);
-    for (int i = 0; i < cd->n_times; ++i) times[i] = (float)cd->times[i];
-    const auto mm = std::minmax_element(times.begin(), times.end());
-    Nodes nv;
-    nv.bind(H, k.S, *mm.first, *mm.second);
-    DirGrids dg;
-    dg.bind(H, k.S, *mm.first, *mm.second, camera_origin_bound(cd));
-    std::vector<int32_t> bstart, bfaces;
-    std::vector<float> bz;
-    std::vector<uint32_t> bmask, brmask;
-    int32_t bins_x = 0, mesh_bins = 0;
-    if (opt_on(OPT_BINS) && primary_bins(H, cd, nv.bounds, bstart, bfaces, bz, bmask, brmask, bins_x, mesh_bins)) {
-        if (bfaces.empty()) { bfaces.push_back(0); bz.push_back(0.0f); }
-        k.S.bin_start = (cptr<int32_t>)bstart.data();
-        k.S.bin_faces = (cptr<int32_t>)bfaces.data();
-        k.S.bin_zmin = (cptr<float>)bz.data();
-        k.S.bin_objmask = (cptr<uint32_t>)bmask.data();
-        k.S.bin_rootmask = (cptr<uint32_t>)brmask.data();
-        k.S.mesh_bins = mesh_bins;
-        k.S.bins_x = bins_x;
-        k.S.bins_on = 1;
-    }
-    std::vector<float> noise;
-    const size_t nsamp = (size_t)cd->n_dof * cd->n_aa;
-    if (cd->jitter == RTX_JITTER_REPLAY) noise.assign(cd->noise, cd->noise + 3 * (size_t)cd->ncols * cd->height * nsamp);
-    k.xs = (cptr<float>)cd->xs; k.ys = (cptr<float>)cd->ys; k.dof_o = (cptr<float>)cd->dof_origins;
-    k.aa_o = (cptr<float>)cd->aa_origins; k.times = (cptr<float>)times.data(); k.noise = (cptr<float>)noise.data();
-    Heavy hv;
-    hv.bind(H, k, bstart);
+    const KParams& k = E.k;
     const int64_t npix = (int64_t)nrows * k.ncols;
 #pragma omp parallel for num_threads(threads > 0 ? threads : 1) schedule(dynamic, 64)
     for (int64_t p = 0; p < npix; ++p) {
@@ -265,20 +202,17 @@ extern "C" int rtx_hostemu_render_rows(const rtx_scene_desc* sd, const rtx_camer
         const HStack hs{hst, 1};
         const int32_t rr = (int32_t)(p / k.ncols), cc = (int32_t)(p % k.ncols);
         // render_pixel's image row is row0 + rr
-        pixel_any(H, k, fb, rows[rr] - rr, rr, cc, tl, fs, hs, k.jitter != RTX_JITTER_OFF, rows[rr & ~7]);
+        pixel_any(E.H, k, fb, rows[rr] - rr, rr, cc, tl, fs, hs, k.jitter != RTX_JITTER_OFF, rows[rr & ~7]);
     }
     return RTX_OK;
 }
 
 extern "C" int rtx_hostemu_intersect(const rtx_scene_desc* sd, int64_t n, const float* ro, const float* rd, double time,
                                      double* t_out, int32_t* obj_out, int32_t* mat_out, float* n_out, float* p_out) {
-    HostScene H;
-    int rc = convert_scene(sd, H);
-    if (rc) return rc;
-    SceneView v{};
-    bind_view(H, v);
-    Nodes nv;
-    nv.bind(H, v, (float)time, (float)time);
+    EmuScene E;
+    if (int rc = E.init(sd, false)) return rc;
+    const HostScene& H = E.H;
+    const SceneView v = E.at((float)time);
     for (int64_t i = 0; i < n; ++i) {
         const f3 o = mk(ro[i], ro[n + i], ro[2 * n + i]);
         const f3 d = mk(rd[i], rd[n + i], rd[2 * n + i]);
@@ -307,13 +241,10 @@ extern "C" int rtx_hostemu_intersect(const rtx_scene_desc* sd, int64_t n, const 
 
 extern "C" int rtx_hostemu_occluded(const rtx_scene_desc* sd, int64_t n, const float* ro, const float* rd,
                                     const double* tmax, double time, uint8_t* occ) {
-    HostScene H;
-    int rc = convert_scene(sd, H);
-    if (rc) return rc;
-    SceneView v{};
-    bind_view(H, v);
-    Nodes nv;
-    nv.bind(H, v, (float)time, (float)time);
+    EmuScene E;
+    if (int rc = E.init(sd, false)) return rc;
+    const HostScene& H = E.H;
+    const SceneView v = E.at((float)time);
     for (int64_t i = 0; i < n; ++i) {
         const f3 o = mk(ro[i], ro[n + i], ro[2 * n + i]);
         const f3 d = mk(rd[i], rd[n + i], rd[2 * n + i]);
@@ -332,20 +263,13 @@ extern "C" int rtx_hostemu_occluded(const rtx_scene_desc* sd, int64_t n, const f
 // with grids = 0 through the BVH walk. Returns -1 if grids = 1 and the light has no grid.
 extern "C" int rtx_hostemu_occluded_light(const rtx_scene_desc* sd, int64_t n, const float* ro, int32_t light,
                                           int32_t grids, uint8_t* occ, int32_t* cells) {
-    HostScene H;
-    int rc = convert_scene(sd, H);
-    if (rc) return rc;
+    EmuScene E;
+    if (int rc = E.init(sd, grids != 0)) return rc;
+    const HostScene& H = E.H;
     if (light < 0 || light >= (int32_t)H.lights.size() || H.lights[light].type != LIGHT_POINT)
         return fail(RTX_ERR_INVALID, "not a point light");
-    SceneView v{};
-    bind_view(H, v);
-    Grids lg;
-    if (grids) {
-        lg.bind(H, v);
-        if (!v.lgrid_on || lg.grids[light].G == 0) return -1;
-    }
-    Nodes nv;
-    nv.bind(H, v, 0.0f, 0.0f);
+    const SceneView v = E.at(0.0f);
+    if (grids && (!v.lgrid_on || E.lg.grids[light].G == 0)) return -1;
     const DLight& L = H.lights[light];
     for (int64_t i = 0; i < n; ++i) {
         const f3 o = mk(ro[i], ro[n + i], ro[2 * n + i]);
@@ -367,15 +291,14 @@ extern "C" int rtx_hostemu_occluded_light(const rtx_scene_desc* sd, int64_t n, c
 // light has no grid. The grid is built for time 0.
 extern "C" int rtx_hostemu_dir_shadow_mask(const rtx_scene_desc* sd, int64_t n, const float* ro, int32_t light,
                                            uint32_t* mask) {
-    HostScene H;
-    int rc = convert_scene(sd, H);
-    if (rc) return rc;
-    if (light < 0 || light >= (int32_t)H.lights.size()) return fail(RTX_ERR_INVALID, "bad light");
-    SceneView v{};
-    bind_view(H, v);
-    DirGrids dg;
-    dg.bind(H, v, 0.0f, 0.0f);
-    if (!v.dsg_on || dg.grids[light].G == 0) return -1;
+    EmuScene E;
+    if (int rc = E.init(sd, false)) return rc;
+    if (light < 0 || light >= (int32_t)E.H.lights.size()) return fail(RTX_ERR_INVALID, "bad light");
+    TimeTables tr;
+    tr.build(E.H, 0.0f, 0.0f, false);
+    if (!tr.grids_on || tr.grids[light].G == 0) return -1;
+    SceneView v = E.view;
+    bind_dir_grids(v, tr.grids.data(), tr.cells_at());
     for (int64_t i = 0; i < n; ++i) {
         const DSCell c = dir_shadow_mask(v, light, mk(ro[i], ro[n + i], ro[2 * n + i]));
         mask[2 * i] = c.obj;
@@ -387,17 +310,10 @@ extern "C" int rtx_hostemu_dir_shadow_mask(const rtx_scene_desc* sd, int64_t n, 
 // The boxes (bits 16-31) whose own shadow test a camera ray's hit on them skips, for
 // directional light `light` and this camera (DSGrid::self_boxes); -1: no grid.
 extern "C" int64_t rtx_hostemu_dsgrid_self(const rtx_scene_desc* sd, const rtx_camera_desc* cd, int32_t light) {
-    HostScene H;
-    if (convert_scene(sd, H)) return -1;
-    std::vector<float> tms(cd->n_times);
-    for (int i = 0; i < cd->n_times; ++i) tms[i] = (float)cd->times[i];
-    const auto tmm = std::minmax_element(tms.begin(), tms.end());
-    SceneView v{};
-    bind_view(H, v);
-    DirGrids dg;
-    dg.bind(H, v, *tmm.first, *tmm.second, camera_origin_bound(cd));
-    if (!v.dsg_on || light < 0 || light >= (int32_t)dg.grids.size() || dg.grids[light].G == 0) return -1;
-    return (int64_t)dg.grids[light].self_boxes;
+    EmuCam E;
+    if (E.init(sd, cd, false)) return -1;
+    if (!E.k.S.dsg_on || light < 0 || light >= (int32_t)E.T.grids.size() || E.T.grids[light].G == 0) return -1;
+    return (int64_t)E.T.grids[light].self_boxes;
 }
 
 // The planes' self-test limits rtx_camera_set builds for this camera (plane_self_limits):
@@ -507,47 +423,17 @@ extern "C" void rtx_hostemu_spec_pow(const float* x, int64_t n, int32_t hardness
 // at most cap bytes (NUL-terminated). tools/jit_offline.py compiles it without a GPU.
 extern "C" int64_t rtx_hostemu_jit_spec(const rtx_scene_desc* sd, const rtx_camera_desc* cd, int32_t cnt, int32_t out8,
                                         char* out, int64_t cap) {
-    HostScene H;
-    if (convert_scene(sd, H)) return -2;
-    KParams k;
-    if (convert_camera(cd, k)) return -2;
-    bind_view(H, k.S);
-    k.S.n_objs_all = (int32_t)H.objs.size();
-    k.S.n_mats = (int32_t)H.mats.size();
-    k.S.n_tris = (int32_t)H.tris.size();
-    k.S.n_leaves = (int32_t)H.leaves.size();
-    Grids lg;
-    lg.bind(H, k.S);
-    std::vector<float> tms(cd->n_times);
-    for (int i = 0; i < cd->n_times; ++i) tms[i] = (float)cd->times[i];
-    const auto tmm = std::minmax_element(tms.begin(), tms.end());
-    DirGrids dg;
-    dg.bind(H, k.S, *tmm.first, *tmm.second, camera_origin_bound(cd));
-    std::vector<int32_t> bstart, bfaces;
-    std::vector<float> bz;
-    std::vector<uint32_t> bmask, brmask;
-    int32_t bins_x = 0, mesh_bins = 0;
-    std::vector<DBound> nodeb;
-    if (!H.nodes.empty()) nodeb = compute_bounds(H.nodes, H.objs, H.tris, *tmm.first, *tmm.second);
-    if (opt_on(OPT_BINS) && primary_bins(H, cd, nodeb, bstart, bfaces, bz, bmask, brmask, bins_x, mesh_bins)) {
-        k.S.bins_on = 1;
-        k.S.mesh_bins = mesh_bins;
-    }
+    EmuCam E;
+    if (E.init(sd, cd, false)) return -2;
+    const HostScene& H = E.H;
+    const KParams& k = E.k;
     const int spp = k.n_dof * k.n_aa * k.n_times;
     const bool spp_mode = use_spp_mode(spp, H.has_ext);
     JitSpec sp;
-    if (!jit_spec("gfx950", k.S, k, scene_traits(H), H.has_mesh, H.has_secondary, H.has_ext, cnt != 0,
+    if (!jit_spec("gfx950", E.view, k, scene_traits(H), H.has_mesh, H.has_secondary, H.has_ext, cnt != 0,
                   k.jitter != RTX_JITTER_OFF, spp_mode, out8 != 0, jit_baked_records(H.objs, H.mats, H.lights), sp))
         return -1;
-    std::string s = sp.name + "\n";
-    for (const auto& o : sp.opts) s += o + "\n";
-    s += "\n" + sp.src;
-    if (out && cap > 0) {
-        const size_t n = std::min((size_t)cap - 1, s.size());
-        memcpy(out, s.data(), n);
-        out[n] = '\0';
-    }
-    return (int64_t)s.size();
+    return spec_text(sp, out, cap);
 }
 
 // The specialized split pass (rtx_api.hip jit_split_spec: pass 0 trace, 1 shadow) librtx.so
@@ -565,15 +451,7 @@ extern "C" int64_t rtx_hostemu_jit_split(const rtx_scene_desc* sd, int32_t pass,
     // (without the camera's counts, jit_fixed_opts: render_split adds them per camera)
     const JitSpec sp = jit_split_spec("gfx950", tables, H.has_mesh, H.has_secondary, cnt != 0, jit != 0, pass,
                                       ((int)opt(OPT_CSG_RAYS) >> pass) & 1, std::vector<std::string>());
-    std::string s = sp.name + "\n";
-    for (const auto& o : sp.opts) s += o + "\n";
-    s += "\n" + sp.src;
-    if (out && cap > 0) {
-        const size_t n = std::min((size_t)cap - 1, s.size());
-        memcpy(out, s.data(), n);
-        out[n] = '\0';
-    }
-    return (int64_t)s.size();
+    return spec_text(sp, out, cap);
 }
 
 // The split hierarchy passes (rtx_split.h trace_sample / shadow_mask / shade_sample) on
@@ -665,43 +543,12 @@ static void split_frame(const KParams& k, const Launch& L0, int64_t npix, int sp
 extern "C" int rtx_hostemu_render_split(const rtx_scene_desc* sd, const rtx_camera_desc* cd, int32_t row0,
                                         int32_t nrows, float* fb, uint64_t* counters, int threads,
                                         int64_t budget, double ratio, int64_t* redone) {
-    HostScene H;
-    int rc = convert_scene(sd, H);
-    if (rc) return rc;
-    KParams k;
-    if ((rc = convert_camera(cd, k))) return rc;
+    EmuCam E;
+    if (int rc = E.init(sd, cd)) return rc;
+    const HostScene& H = E.H;
+    const KParams& k = E.k;
     if (row0 < 0 || nrows < 0 || row0 + nrows > cd->height) return fail(RTX_ERR_INVALID, "bad rows");
     if (!H.has_ext) return fail(RTX_ERR_INVALID, "the split passes serve hierarchy/texture scenes");
-    bind_view(H, k.S);
-    Grids lg;
-    lg.bind(H, k.S);
-    std::vector<float> times(cd->n_times);
-    for (int i = 0; i < cd->n_times; ++i) times[i] = (float)cd->times[i];
-    const auto mm = std::minmax_element(times.begin(), times.end());
-    Nodes nv;
-    nv.bind(H, k.S, *mm.first, *mm.second);
-    DirGrids dg;
-    dg.bind(H, k.S, *mm.first, *mm.second, camera_origin_bound(cd));
-    std::vector<int32_t> bstart, bfaces;
-    std::vector<float> bz;
-    std::vector<uint32_t> bmask, brmask;
-    int32_t bins_x = 0, mesh_bins = 0;
-    if (opt_on(OPT_BINS) && primary_bins(H, cd, nv.bounds, bstart, bfaces, bz, bmask, brmask, bins_x, mesh_bins)) {
-        if (bfaces.empty()) { bfaces.push_back(0); bz.push_back(0.0f); }
-        k.S.bin_start = (cptr<int32_t>)bstart.data();
-        k.S.bin_faces = (cptr<int32_t>)bfaces.data();
-        k.S.bin_zmin = (cptr<float>)bz.data();
-        k.S.bin_objmask = (cptr<uint32_t>)bmask.data();
-        k.S.bin_rootmask = (cptr<uint32_t>)brmask.data();
-        k.S.mesh_bins = mesh_bins;
-        k.S.bins_x = bins_x;
-        k.S.bins_on = 1;
-    }
-    std::vector<float> noise;
-    const size_t nsamp = (size_t)cd->n_dof * cd->n_aa;
-    if (cd->jitter == RTX_JITTER_REPLAY) noise.assign(cd->noise, cd->noise + 3 * (size_t)cd->ncols * cd->height * nsamp);
-    k.xs = (cptr<float>)cd->xs; k.ys = (cptr<float>)cd->ys; k.dof_o = (cptr<float>)cd->dof_origins;
-    k.aa_o = (cptr<float>)cd->aa_origins; k.times = (cptr<float>)times.data(); k.noise = (cptr<float>)noise.data();
     Launch L{};
     L.row0 = row0;
     L.nrows = nrows;
@@ -727,26 +574,18 @@ extern "C" int rtx_hostemu_render_split(const rtx_scene_desc* sd, const rtx_came
 
 // The primary-ray bins rtx_camera_set builds for a camera (rtx_api.hip primary_bins): per
 // 8x8 tile its sphere/box mask and its number of candidate mesh faces. Returns the number
-// of bins (0: the camera has none).
+// of bins (0: the camera has none, as under option bins 0: the tables are rtx_camera_set's).
 extern "C" int64_t rtx_hostemu_bins(const rtx_scene_desc* sd, const rtx_camera_desc* cd, uint32_t* mask,
                                     int32_t* nfaces, uint32_t* rmask, int64_t cap) {
-    HostScene H;
-    if (convert_scene(sd, H)) return -1;
-    std::vector<int32_t> bstart, bfaces;
-    std::vector<float> bz;
-    std::vector<uint32_t> bmask, brmask;
-    int32_t bins_x = 0, mesh_bins = 0;
-    std::vector<float> tms(cd->n_times);
-    for (int i = 0; i < cd->n_times; ++i) tms[i] = (float)cd->times[i];
-    const auto tmm = std::minmax_element(tms.begin(), tms.end());
-    std::vector<DBound> nodeb;
-    if (!H.nodes.empty()) nodeb = compute_bounds(H.nodes, H.objs, H.tris, *tmm.first, *tmm.second);
-    if (!primary_bins(H, cd, nodeb, bstart, bfaces, bz, bmask, brmask, bins_x, mesh_bins)) return 0;
-    const int64_t n = (int64_t)bmask.size();
+    EmuCam E;
+    if (E.init(sd, cd, false)) return -1;
+    const CamTables& T = E.T;
+    if (!T.bins) return 0;
+    const int64_t n = (int64_t)T.brmask.size();
     for (int64_t b = 0; b < n && b < cap; ++b) {
-        mask[b] = bmask[b];
-        nfaces[b] = mesh_bins && b + 1 < (int64_t)bstart.size() ? bstart[b + 1] - bstart[b] : 0;
-        if (rmask) rmask[b] = brmask[b];
+        mask[b] = T.bmask[b];
+        nfaces[b] = T.mesh_bins && b + 1 < (int64_t)T.bstart.size() ? T.bstart[b + 1] - T.bstart[b] : 0;
+        if (rmask) rmask[b] = T.brmask[b];
     }
     return n;
 }
@@ -757,8 +596,7 @@ extern "C" int64_t rtx_hostemu_bins(const rtx_scene_desc* sd, const rtx_camera_d
 extern "C" int rtx_hostemu_camera_cost(const rtx_scene_desc* sd, const rtx_camera_desc* cd, int reps, double* ms) {
     HostScene H;
     if (int rc = convert_scene(sd, H)) return rc;
-    std::vector<float> tms(cd->n_times);
-    for (int i = 0; i < cd->n_times; ++i) tms[i] = (float)cd->times[i];
+    const std::vector<float> tms = camera_times(cd);
     const auto tmm = std::minmax_element(tms.begin(), tms.end());
     const double omax = camera_origin_bound(cd);
     for (int q = 0; q < 5; ++q) ms[q] = INFINITY;

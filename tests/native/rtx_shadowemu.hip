@@ -5,45 +5,12 @@
 #include "rtx_hostemu.hip"
 
 namespace {
-// The camera's tables bound to k as rtx_camera_set does for a flat scene (no mesh, no
-// hierarchy): times, primary bins, plane self tests, directional grids.
-struct FlatCam {
-    HostScene H;
-    KParams k;
-    std::vector<float> times;
-    DirGrids dg;
-    std::vector<int32_t> bstart, bfaces;
-    std::vector<float> bz;
-    std::vector<uint32_t> bmask, brmask, bshadow;
-    int32_t bins_x = 0;
-    bool have_bins = false;
-    int init(const rtx_scene_desc* sd, const rtx_camera_desc* cd) {
-        int rc = convert_scene(sd, H);
-        if (rc) return rc;
-        if ((rc = convert_camera(cd, k))) return rc;
-        if (H.has_mesh || H.has_ext) return fail(RTX_ERR_INVALID, "shadowemu: flat scenes only");
-        bind_view(H, k.S);
-        times = camera_times(cd);
-        const auto mm = std::minmax_element(times.begin(), times.end());
-        dg.bind(H, k.S, *mm.first, *mm.second, camera_origin_bound(cd));
-        int32_t mesh_bins = 0;
-        have_bins = opt_on(OPT_BINS) && primary_bins(H, cd, {}, bstart, bfaces, bz, bmask, brmask, bins_x, mesh_bins);
-        if (have_bins) {
-            bfaces.push_back(0);
-            bz.push_back(0.0f);
-            k.S.bin_start = (cptr<int32_t>)bstart.data();
-            k.S.bin_faces = (cptr<int32_t>)bfaces.data();
-            k.S.bin_zmin = (cptr<float>)bz.data();
-            k.S.bin_objmask = (cptr<uint32_t>)bmask.data();
-            k.S.bin_rootmask = (cptr<uint32_t>)brmask.data();
-            k.S.bins_x = bins_x;
-            k.S.bins_on = 1;
-        }
-        k.xs = (cptr<float>)cd->xs; k.ys = (cptr<float>)cd->ys; k.dof_o = (cptr<float>)cd->dof_origins;
-        k.aa_o = (cptr<float>)cd->aa_origins; k.times = (cptr<float>)times.data();
-        return RTX_OK;
-    }
-};
+// The emulated camera of a flat scene (no mesh, no hierarchy).
+int flat_cam(EmuCam& F, const rtx_scene_desc* sd, const rtx_camera_desc* cd) {
+    if (int rc = F.init(sd, cd)) return rc;
+    if (F.H.has_mesh || F.H.has_ext) return fail(RTX_ERR_INVALID, "shadowemu: flat scenes only");
+    return RTX_OK;
+}
 }  // namespace
 
 // The shadow bins of a camera: out[bin * n_lights + light] (margin: shadow_bins' test knob,
@@ -51,14 +18,14 @@ struct FlatCam {
 // the host time of the build (best of reps).
 extern "C" int64_t rtx_shadowemu_masks(const rtx_scene_desc* sd, const rtx_camera_desc* cd, double margin, uint32_t* out,
                                        int64_t cap, int reps, double* ms) {
-    FlatCam F;
-    if (F.init(sd, cd)) return -1;
-    if (!F.have_bins) return 0;
+    EmuCam F;
+    if (flat_cam(F, sd, cd)) return -1;
+    if (!F.T.bins) return 0;
     std::vector<uint32_t> m;
     double best = INFINITY;
     for (int r = 0; r < (reps > 0 ? reps : 1); ++r) {
         const auto t0 = std::chrono::steady_clock::now();
-        if (!shadow_bins(F.H, cd, F.bmask, F.bins_x, m, margin)) return 0;
+        if (!shadow_bins(F.H, cd, F.T.bmask, F.T.bins_x, m, margin)) return 0;
         best = std::min(best, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }
     if (ms) *ms = best;
@@ -72,10 +39,9 @@ extern "C" int64_t rtx_shadowemu_masks(const rtx_scene_desc* sd, const rtx_camer
 // occluding; res[1]: those whose bit in masks[bin * n_lights + light] is clear (the table
 // would have skipped a test that passes); res[2]: level-0 hits.
 extern "C" int rtx_shadowemu_check(const rtx_scene_desc* sd, const rtx_camera_desc* cd, const uint32_t* masks, int64_t* res) {
-    FlatCam F;
-    int rc = F.init(sd, cd);
-    if (rc) return rc;
-    if (!F.have_bins) return fail(RTX_ERR_INVALID, "shadowemu: the camera has no bins");
+    EmuCam F;
+    if (int rc = flat_cam(F, sd, cd)) return rc;
+    if (!F.T.bins) return fail(RTX_ERR_INVALID, "shadowemu: the camera has no bins");
     const KParams& k = F.k;
     const HostScene& H = F.H;
     const int32_t NL = H.n_lights;
@@ -123,42 +89,18 @@ extern "C" int rtx_shadowemu_check(const rtx_scene_desc* sd, const rtx_camera_de
     return RTX_OK;
 }
 
+// (render_block jitters as the camera says, as rtx_hostemu_render does; the pinhole cameras
+// that get shadow bins have none.)
 // rtx_hostemu_render of a flat scene with the camera's shadow bins bound (use_masks) or not.
 // *bound: 1 when the frame read the table.
 extern "C" int rtx_shadowemu_render(const rtx_scene_desc* sd, const rtx_camera_desc* cd, int use_masks, float* fb,
                                     uint64_t* counters, int threads, int* bound_out) {
-    FlatCam F;
-    int rc = F.init(sd, cd);
-    if (rc) return rc;
-    int bound = 0;
-    if (use_masks && F.have_bins && shadow_bins(F.H, cd, F.bmask, F.bins_x, F.bshadow)) {
-        F.k.S.bin_shadow = (cptr<uint32_t>)F.bshadow.data();
-        bound = 1;
-    }
-    const KParams& k = F.k;
-    const int64_t npix = (int64_t)k.height * k.ncols;
+    EmuCam F;
+    if (int rc = flat_cam(F, sd, cd)) return rc;
+    if (!use_masks) F.k.S.bin_shadow = nullptr;
     uint64_t tot[RTX_COUNTERS] = {};
-#pragma omp parallel num_threads(threads > 0 ? threads : 1)
-    {
-        uint64_t loc[RTX_COUNTERS] = {};
-#pragma omp for schedule(dynamic, 64)
-        for (int64_t p = 0; p < npix; ++p) {
-            Tally tl = {};
-            float frames[kMaxDepth * 4];
-            float hst[kMaxHLevels * 9];
-            const FrameStack fs{frames, 1};
-            const HStack hs{hst, 1};
-            const int32_t rr = (int32_t)(p / k.ncols), cc = (int32_t)(p % k.ncols);
-            pixel_any(F.H, k, fb, 0, rr, cc, tl, fs, hs, false, rr & ~7);
-            for (int q = 0; q < kMaxDepth; ++q) loc[q] += tl.cast[q];
-            loc[RTX_CNT_SHADOW] += tl.shadow;
-            loc[RTX_CNT_SHADE] += tl.shade;
-            loc[RTX_CNT_TRI] += tl.tri;
-        }
-#pragma omp critical
-        for (int q = 0; q < RTX_COUNTERS; ++q) tot[q] += loc[q];
-    }
+    render_block(F, 0, F.k.height, fb, tot, threads);
     for (int q = 0; q < RTX_COUNTERS; ++q) counters[q] = tot[q];
-    *bound_out = bound;
+    *bound_out = F.k.S.bin_shadow != nullptr;
     return RTX_OK;
 }
