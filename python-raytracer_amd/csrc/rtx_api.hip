@@ -81,7 +81,7 @@ enum Opt {
     OPT_SELF_SKIP, OPT_TILE_SCHED, OPT_XCD_MAP, OPT_TILE_BLOCK, OPT_PRIM_ORIGIN, OPT_SPP, OPT_SPP_MIN, OPT_JIT, OPT_JIT_BAKE, OPT_JIT_EXT,
     OPT_JIT_DUMP, OPT_JIT_IDLE_BAKED, OPT_JIT_DISK_BAKED, OPT_JIT_CACHE, OPT_JIT_FLAGS, OPT_JIT_ILP, OPT_JIT_ASYNC,
     OPT_DEV_BINS, OPT_CHUNK_MODE, OPT_BIN_LDS, OPT_JIT_CSG, OPT_CSG_RAYS, OPT_CSG_SHADE, OPT_SETUP_LOG, OPT_SHADOW_BINS,
-    OPT_UNIFORM_HIT, OPT_COUNT
+    OPT_UNIFORM_HIT, OPT_RAY_TABLE, OPT_RAY_TABLE_MAX_MB, OPT_COUNT
 };
 struct OptDef {
     const char* name;
@@ -124,6 +124,8 @@ constexpr OptDef kOpts[OPT_COUNT] = {
     {"setup_log", 0, false},                  // print the host time of each rtx_camera_set step
     {"shadow_bins", 1, false},                // per-bin occluder masks of level-0 shadow rays (2: scenes with secondary rays too)
     {"uniform_hit", 1, false},                // wave-uniform hits shaded from literal records (scenes of few objects, no secondary rays)
+    {"ray_table", 1, false},                  // per-camera table of primary-ray directions (one-sample, unjittered cameras; 4: secondary rays and meshes without face boxes too)
+    {"ray_table_max_mb", 64, false},          // the largest table built, MiB of device memory (larger strips compute their rays)
 };
 struct OptVal {
     double v;
@@ -2159,6 +2161,8 @@ struct CamTables {
     bool sbins = false;      // shadow bins
     bool tsched = false;     // the measured tile schedule
     bool po = false;         // the primary rays' origin-only terms
+    bool rays = false;       // the primary rays' direction table
+    bool rays_dev = false;   // ... filled on the device after the upload (k_ray_dirs), else by bind()
 
     // (the order the tables are built in: they are freed in the reverse order, the large
     // mask vectors together, after the upload)
@@ -2179,11 +2183,13 @@ struct CamTables {
     size_t host_bytes = 0;  // the staged part: what precedes the segments filled later
     size_t o_xs = 0, o_ys = 0, o_dof = 0, o_aa = 0, o_times = 0, o_noise = 0, o_bounds = 0, o_pself = 0, o_dsg = 0;
     size_t o_bstart = 0, o_bfaces = 0, o_bz = 0, o_bmask = 0, o_bheavy = 0, o_hitems = 0, o_mhits = 0, o_sbs = 0;
-    size_t o_bshadow = 0, o_tperm = 0, o_ttime = 0, o_kp = 0;
+    size_t o_bshadow = 0, o_tperm = 0, o_ttime = 0, o_kp = 0, o_rays = 0, rays_bytes = 0;
 
     // times_: camera_times(c), which the caller has for the time range
+    // on_device: the caller fills the direction table on the device (the library); otherwise
+    // bind() fills it in the caller's buffer (the host emulation)
     int build(const HostScene& H, const rtx_camera_desc* c, std::vector<float> times_, const TimeTables& tr,
-              const DevFaces& dev1, SetupLog& slog) {
+              const DevFaces& dev1, SetupLog& slog, bool on_device = false) {
         const size_t nsamp = (size_t)c->n_dof * c->n_aa;
         const double omax = camera_origin_bound(c);
         times = std::move(times_);
@@ -2255,6 +2261,25 @@ struct CamTables {
             o_tperm = st.put(ident);
         }
         o_kp = st.put(nullptr, sizeof(KParams));
+        // The primary rays' direction table (rtx_kernels.h ray_slot; option ray_table 0: none):
+        // cameras whose primary_dir depends on the pixel alone -- one sample per pixel, no jitter --
+        // of flat scenes (the hierarchy / texture kernels are not specialized per camera). Three
+        // fp32 per pixel of the strip's whole 8x8 tiles, up to ray_table_max_mb MiB: the cap
+        // bounds the device memory a camera may take for it (1920x1080 takes 23.7 MiB,
+        // 2048x1024 24 MiB, 3840x2160 94.9 MiB), it is not a measured break-even.
+        // Scenes with secondary rays, and meshes without face boxes (the mesh kernels of 4 waves
+        // per SIMD, jit_spec), get none: measured slower with it (MirrorRefraction 1080p 34.8 ->
+        // 36.5 us, the 81,920-face mesh 148.2 -> 150.4 us; TwoSpheresPlane 17.85 -> 16.53 us,
+        // TorusMesh 43.8 -> 41.7 us). Option ray_table 4 gives them the table too
+        // (the tests, and a later measurement).
+        bool boxed = true;  // every top-level mesh has face boxes (SceneTraits::fc_mode 1), or there is none
+        for (const DObj& o : H.objs) boxed = boxed && (o.type != RTX_MESH || o.face_cull);
+        rays_bytes = sizeof(float) * 3 * (size_t)ray_table_slots(c->height, c->ncols);
+        rays = opt_on(OPT_RAY_TABLE) && c->n_dof == 1 && c->n_aa == 1 && c->n_times == 1 &&
+               c->jitter == RTX_JITTER_OFF && !H.has_ext && ((!H.has_secondary && boxed) || opt(OPT_RAY_TABLE) == 4.0) &&
+               (double)rays_bytes <= opt(OPT_RAY_TABLE_MAX_MB) * 1048576.0;
+        rays_dev = rays && on_device;
+        if (rays && !rays_dev) o_rays = st.put(nullptr, rays_bytes);
         // the segments filled after the upload, last: the host stages (and uploads) only what
         // precedes them
         host_bytes = st.size();
@@ -2265,6 +2290,7 @@ struct CamTables {
         if (heavy) o_mhits = st.put(nullptr, sizeof(uint2) * 64 * hitems.size(), true);
         if (sbins) o_bshadow = st.put(nullptr, sizeof(uint32_t) * (size_t)sbs.bins_x * sbs.bins_y * sbs.NL, true);
         if (tsched) o_ttime = st.put(nullptr, sizeof(uint32_t) * nw, true);
+        if (rays_dev) o_rays = st.put(nullptr, rays_bytes, true);
         slog.mark("tile schedule", st.size());
         // one sample, no jitter, static scene: every primary ray starts at aa_o[0], so its
         // origin-only plane and sphere terms are per-frame constants (closest_hit's fp32
@@ -2326,6 +2352,15 @@ struct CamTables {
         // refreshed with the tables on every upload
         set3(k.dof0, c->dof_origins);
         set3(k.aa0, c->aa_origins);
+        if (rays) k.ray_dirs = (cptr<float>)(D + o_rays);
+        if (rays && !rays_dev) {  // (host memory: the entries k_ray_dirs computes)
+            float* out = reinterpret_cast<float*>(D + o_rays);
+            for (int64_t q = 0, n = ray_table_slots(c->height, c->ncols); q < n; ++q) {
+                const f3 d = ray_table_entry(k, q);
+                float* o = out + 3 * q;
+                o[0] = d.x; o[1] = d.y; o[2] = d.z;
+            }
+        }
     }
 };
 
@@ -2617,6 +2652,13 @@ bool jit_spec(const std::string& arch, const SceneView& v, const KParams& kp, co
     opts.push_back(std::string("-DRTX_PRIMARY_BINS=") + (kp.S.bins_on ? "1" : "0"));
     // (only kernels of cameras with shadow bins: the others' option lists stay as they were)
     if (kp.S.bins_on && kp.S.bin_shadow != nullptr) opts.push_back("-DRTX_SHADOW_BINS=1");
+    // (likewise, only kernels of cameras with a direction table: one sample, no jitter)
+    if (!spp && !ext && kp.ray_dirs != nullptr && kp.n_dof * kp.n_aa * kp.n_times == 1 && kp.jitter == RTX_JITTER_OFF) {
+        opts.push_back("-DRTX_RAY_TABLE=1");
+        // with it, the framebuffer store as a global store instead of a flat one (rtx_kernels.h
+        // put_channel): measured equal on TwoSpheresPlane and TorusMesh
+        opts.push_back("-DRTX_FB_GLOBAL=1");
+    }
     // a mesh's face bins read through LDS (rtx_trace.h BinLds; option bin_lds)
     if (mesh && !ext && kp.S.bins_on && kp.S.mesh_bins && opt_on(OPT_BIN_LDS)) opts.push_back("-DRTX_BIN_LDS=1");
     opts.push_back(std::string("-DRTX_LIGHT_GRIDS=") + (v.lgrid_on ? "1" : "0"));
@@ -3108,6 +3150,10 @@ struct rtx_scene {
     int tile_sched = 0;
     bool tile_xcd = false;            // the schedule table's layout (option xcd_map when sorted)
     hipEvent_t tile_event = nullptr;  // recorded after the measuring launch
+    // the direction table's fill (k_ray_dirs, null stream): recorded after it by rtx_camera_set,
+    // which does not wait for it; renders order their stream behind it while it is pending
+    hipEvent_t rays_event = nullptr;
+    bool rays_pending = false;
     // the split hierarchy passes (rtx_split.h, render_split): the record arrays of one
     // chunk (kept while the scene lives, reused by every frame), the per-chunk append
     // counters of a frame, the per-block redo flags (all zero between renders), and what the
@@ -3219,6 +3265,7 @@ void free_scene(rtx_scene* s) {
     if (s->split_done) (void)hipEventDestroy(s->split_done);
     (void)hipHostFree(s->h_split_count);
     if (s->tile_event) (void)hipEventDestroy(s->tile_event);
+    if (s->rays_event) (void)hipEventDestroy(s->rays_event);
     for (void* p : {s->d_objs, s->d_tris, s->d_trins, s->d_fboxes, s->d_mats, s->d_lights, s->d_leaves, s->d_tri_orig, s->d_nodes, s->d_nmat,
                     s->d_texels, s->d_lut, s->d_bounds_abi, s->d_lgrid, s->d_lg_start, s->d_lg_faces, s->d_lg_d2})
         (void)hipFree(p);
@@ -3351,6 +3398,8 @@ int32_t rtx_jit_wait(rtx_scene* s, int32_t block) {
         jit_poll(r, block != 0);
         n += r.pending ? 1 : 0;
     }
+    // (the call that precedes a capture: the direction table's fill is done with, too)
+    if (block && s->rays_pending && hipEventSynchronize(s->rays_event) == hipSuccess) s->rays_pending = false;
     return n;
 }
 
@@ -3514,7 +3563,7 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
     auto dev1 = [&](int32_t bins_x, std::vector<int32_t>& start, int32_t* npairs, int32_t* mesh_bins) {
         return mesh_bins_dev1(s, c, bins_x, start, npairs, mesh_bins, slog);
     };
-    if ((rc = T.build(H, c, std::move(times), tr, std::ref(dev1), slog))) return rc;
+    if ((rc = T.build(H, c, std::move(times), tr, std::ref(dev1), slog, true))) return rc;
     // one device buffer for all of it, reused while large enough; its old contents may still
     // be read by frames of the previous camera
     (void)hipDeviceSynchronize();
@@ -3556,6 +3605,20 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
         RTX_HIP(hipGetLastError());
         RTX_HIP(hipStreamSynchronize(nullptr));
         slog.mark("shadow bins (device)");
+    }
+    if (T.rays) {  // the direction table, from the tables and parameters just uploaded (no host wait)
+        const int64_t nslots = ray_table_slots(k.height, k.ncols);
+        hipLaunchKernelGGL(k_ray_dirs, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, nullptr,
+                           reinterpret_cast<const KParams*>(D + T.o_kp), reinterpret_cast<float*>(D + T.o_rays), nslots);
+        RTX_HIP(hipGetLastError());
+        // a render may come on any stream, and a non-blocking one has no order with the null
+        // stream: render_launch makes its stream wait for this event
+        if (!s->rays_event) RTX_HIP(hipEventCreateWithFlags(&s->rays_event, hipEventDisableTiming));
+        RTX_HIP(hipEventRecord(s->rays_event, nullptr));
+        s->rays_pending = true;
+        char step[64];
+        snprintf(step, sizeof(step), "ray table (device) [%zu B]", T.rays_bytes);
+        slog.mark(step);
     }
     if (T.dev_faces) {
         if ((rc = mesh_bins_dev2(s, T.bins_x, (int32_t)(T.bstart.size() - 1), T.dev_pairs,
@@ -4030,6 +4093,7 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
         L.ys = s->kp.ys;
         L.bin_objmask = s->kp.S.bin_objmask;
         L.bin_shadow = s->kp.S.bin_shadow;
+        L.ray_dirs = s->kp.ray_dirs;
     }
     // the heavy tiles' chunks of a tile-mapped launch, just before it (the sample-parallel
     // and split kernels pass no pixel-in-tile and walk the lists). One pass serves every
@@ -4054,6 +4118,14 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
         jit_poll(rs, false);  // (a capture records the kernel that runs now: no module load inside it)
     }
     if (rs.fn && jit_enabled()) {
+        // the camera's direction table may still be filling (rtx_camera_set does not wait): this
+        // stream's work goes behind the fill until the fill is seen done. A capture records no
+        // wait: the eager render that precedes it on the stream, or
+        // rtx_jit_wait, has ordered the fill before it.
+        if (s->rays_pending && L.ray_dirs != nullptr && !stream_capturing(st)) {
+            if (hipEventQuery(s->rays_event) == hipSuccess) s->rays_pending = false;
+            else RTX_HIP(hipStreamWaitEvent(st, s->rays_event, 0));
+        }
         void* args[] = {(void*)&kp, (void*)&L};
         if (!rs.xcd) L.xcd = 0;  // (a kernel compiled without the map keeps the blocks' own order)
         // whole-frame launches follow the measured tile schedule

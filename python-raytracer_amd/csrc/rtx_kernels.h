@@ -52,6 +52,9 @@ struct alignas(64) KParams {
     cptr<int32_t> tile_perm;
     unsigned int* tile_time;
     int32_t tile_n;
+    // the camera's primary-ray direction table (ray_slot below; rtx_api.hip CamTables::rays):
+    // primary_dir of every pixel of the strip, or null (the camera is outside the class)
+    cptr<float> ray_dirs;
 };
 
 template <bool COUNT>
@@ -95,6 +98,46 @@ RTX_HD f3 pixel_focal(const KParams& P, int32_t cc, int j) {
     // base_ray_direction = normalize(x * u + y * v - d * w)  (scene.py:54)
     const f3 bdir = normalize(sub(add(scale(ld3(P.u), fx), scale(ld3(P.v), fy)), ld3(P.dw)));
     return add(ld3(P.pos), scale(bdir, P.focal));  // scene.py:55
+}
+
+// scene.py:58: the direction of DOF sample kd's rays through pixel (column cc, reference row
+// j), from that sample's lens origin toward the pixel's focal point. One-sample kernels take
+// the origin from the camera block's copy.
+RTX_HD f3 primary_dir(const KParams& P, int32_t cc, int j, int kd = 0) {
+    const f3 focal = pixel_focal(P, cc, j);
+#if RTX_WAVE_HEAD  // (one sample: the camera block's copy of dof_o[0])
+    return normalize(sub(focal, ld3(P.dof0)));
+#else
+    return normalize(sub(focal, ld3(P.dof_o + 3 * kd)));
+#endif
+}
+
+// The direction table of a one-sample, unjittered camera (KParams::ray_dirs): primary_dir
+// depends on the camera and the pixel only, so rtx_camera_set computes it once per pixel
+// (k_ray_dirs) and the scene-specialized kernels of such cameras (RTX_RAY_TABLE, rtx_api.hip
+// jit_spec) read it instead of computing it in every frame. Three fp32 per pixel, tile-major:
+// the slot of image row r (row 0 = top), strip column cc. An 8x8 tile on the 8-row grid is
+// 768 contiguous bytes, one 12-byte load per lane; a tile off the grid (a row block with
+// row0 % 8 != 0) reads parts of two. Ragged right and bottom tiles are allocated whole.
+#ifndef RTX_RAY_TABLE
+#define RTX_RAY_TABLE 0
+#endif
+RTX_HD uint32_t ray_slot(int32_t r, int32_t cc, int32_t ncols) {
+    const uint32_t tiles_x = (uint32_t)(ncols + 7) >> 3;
+    return (((uint32_t)r >> 3) * tiles_x + ((uint32_t)cc >> 3)) * 64u + ((uint32_t)r & 7u) * 8u + ((uint32_t)cc & 7u);
+}
+__host__ __device__ inline int64_t ray_table_slots(int32_t height, int32_t ncols) {
+    return (int64_t)((height + 7) >> 3) * ((ncols + 7) >> 3) * 64;
+}
+// Slot s of the table (k_ray_dirs on the device, a loop in the host emulation). The slots of
+// a ragged tile that lie outside the image take the nearest pixel's direction; no rendered
+// pixel reads them.
+RTX_HD f3 ray_table_entry(const KParams& P, int64_t s) {
+    const int32_t tiles_x = (P.ncols + 7) >> 3;
+    const int32_t tile = (int32_t)(s >> 6), lane = (int32_t)(s & 63);
+    const int32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int32_t r = ty * 8 + (lane >> 3), cc = tx * 8 + (lane & 7);
+    return primary_dir(P, cc < P.ncols ? cc : P.ncols - 1, P.height - 1 - (r < P.height ? r : P.height - 1));
 }
 
 #ifdef RTX_FIXED_JMODE  // scene-specialized kernels pin the jitter mode
@@ -172,11 +215,22 @@ RTX_HD float sample_mean(const KParams& P, float c) {
 #ifndef RTX_OUT8
 #define RTX_OUT8 0
 #endif
+// RTX_FB_GLOBAL (the kernels with a direction table, rtx_api.hip jit_spec): the fp32 store through
+// a pointer typed as global memory. The framebuffer pointer loses its address space in
+// pin_uniform64's integer round trip, so the store is otherwise a flat one.
+#ifndef RTX_FB_GLOBAL
+#define RTX_FB_GLOBAL 0
+#endif
 RTX_HD void put_channel(float* fb, int64_t i, float v) {
     if (RTX_OUT8)
         reinterpret_cast<uint8_t*>(fb)[i] = (uint8_t)(int)((double)v * 255.0);
+#if RTX_FB_GLOBAL && defined(__HIP_DEVICE_COMPILE__)
+    else
+        ((__attribute__((address_space(1))) float*)fb)[i] = v;
+#else
     else
         fb[i] = v;
+#endif
 }
 
 // Multi-sample kernels re-read the scene records in every sample instead of keeping
@@ -238,7 +292,8 @@ RTX_HD SceneView sample_scene(const SceneView& S0) {
 // times (time_base below; 0 for every camera without a sequence).
 template <bool MESH, bool SEC, bool X, bool COUNT, bool JIT>
 RTX_HD void render_pixel(const KParams& P, float* fb, int32_t row0, int32_t rr, int32_t cc, Tally& tl,
-                         const FrameStack& fs, const HStack& hs, int32_t bin = -1, int32_t tb = 0) {
+                         const FrameStack& fs, const HStack& hs, int32_t bin = -1, int32_t tb = 0,
+                         const f3* tdir = nullptr) {
 #ifdef RTX_FIXED_NCOLS  // (render_body's)
     const int32_t ncols = RTX_FIXED_NCOLS;
 #else
@@ -275,11 +330,16 @@ RTX_HD void render_pixel(const KParams& P, float* fb, int32_t row0, int32_t rr, 
 #if defined(__HIP_DEVICE_COMPILE__)
         if (RTX_RELOAD_RECORDS) asm volatile("" : "+v"(cc_k), "+v"(j_k));
 #endif
-        const f3 focal = pixel_focal(P, cc_k, j_k);
-#if RTX_WAVE_HEAD  // (one sample: the camera block's copy of dof_o[0])
-        const f3 ddir = normalize(sub(focal, ld3(P.dof0)));  // scene.py:58
+#if RTX_RAY_TABLE  // the pixel's table entry, which render_body read at the wave's start
+        (void)cc_k; (void)j_k;
+        const f3 ddir = *tdir;
+#elif !defined(__HIP_DEVICE_COMPILE__)  // (the host emulation reads the camera's table, if it has one)
+        (void)tdir;
+        const f3 ddir = P.ray_dirs != nullptr ? ld3(P.ray_dirs + 3 * (int64_t)ray_slot(row0 + rr, cc, ncols))
+                                              : primary_dir(P, cc_k, j_k, kd);  // scene.py:58
 #else
-        const f3 ddir = normalize(sub(focal, ld3(P.dof_o + 3 * kd)));  // scene.py:58
+        (void)tdir;
+        const f3 ddir = primary_dir(P, cc_k, j_k, kd);  // scene.py:58
 #endif
 #pragma unroll 1
         for (int ka = 0; ka < RTX_NAA(P); ++ka) {
@@ -332,7 +392,7 @@ RTX_HD uint2 mesh_chunk(const KParams& P, int32_t bin, int32_t c, int lane) {
     const int32_t row = ty * 8 + (lane >> 3), cc = tx * 8 + (lane & 7);
     const bool active = row < P.height && cc < P.ncols;
     const int j = P.height - 1 - (active ? row : 0);
-    const f3 d = normalize(sub(pixel_focal(P, active ? cc : 0, j), ld3(P.dof_o)));  // scene.py:58
+    const f3 d = primary_dir(P, active ? cc : 0, j);  // scene.py:58
     const f3 o = ld3(P.aa_o);  // scene.py:60-61 (one sample, no jitter)
     const int32_t oi = S.n_plane + S.n_sphere + S.n_box;  // the scene's one top-level mesh
     const DObj ob = S.objs[oi];
@@ -392,7 +452,7 @@ __device__ __forceinline__ uint2 mesh_chunk_lds(const KParams& P, int32_t bin, i
     }
     __syncthreads();
     const int j = P.height - 1 - (active ? row : 0);
-    const f3 d = normalize(sub(pixel_focal(P, active ? cc : 0, j), ld3(P.dof_o)));  // scene.py:58
+    const f3 d = primary_dir(P, active ? cc : 0, j);  // scene.py:58
     const f3 o = ld3(P.aa_o);  // scene.py:60-61 (one sample, no jitter)
     const float time = P.times[0];  // (as mesh_chunk: static geometry)
     const RayInv ri = ray_inv(o, d);
@@ -446,6 +506,7 @@ struct Launch {
     // addresses its tile's entries from the kernel arguments alone (render_body)
     cptr<float> xs, ys;
     cptr<uint32_t> bin_objmask, bin_shadow;
+    cptr<float> ray_dirs;  // (KParams::ray_dirs)
 };
 
 // This block's framebuffer (frame blockIdx.y of a batched launch; the only frame otherwise).
@@ -713,8 +774,30 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
     // KParams comes from the camera block (dof0 / aa0: the only origins of a one-sample
     // camera) or is addressed from Launch's copies of the table pointers.
     KParams Q = *Pp;
+#if RTX_RAY_TABLE
+    // The pixel's direction from the camera's table: its address needs the kernel arguments
+    // and the wave's ids only, so the load goes out ahead of the wait for the camera block
+    // (behind it measured 0.25 us slower). The row is held inside the launch's rows:
+    // lanes below a ragged bottom edge, and waves past the last tile, read an entry of the
+    // last row (the columns of a ragged right tile have slots of their own). A kernel with a
+    // tile schedule knows its tile only after the permutation's entry (below).
+    static_assert(RTX_TILE == 1 && RTX_PPL == 1, "one 8x8 tile per wave");
+    const cptr<float> tdirs = L.ray_dirs;
+    auto table_dir = [&](const PixelRC& px) {
+        const int32_t rq = px.r < L.nrows ? px.r : L.nrows - 1;
+        return ld3(tdirs + 3u * ray_slot(image_row(L, rq), px.c, ncols));
+    };
+    f3 tdir = mk(0.0f, 0.0f, 0.0f);
+#if !RTX_TILE_SCHED
+    const PixelRC px_early = pixel_rc<B>(ncols, 0, L.perm, L.xcd);
+    tdir = table_dir(px_early);
+#endif
+    Q.xs = nullptr;  // (never read: the table stands for both)
+    Q.ys = nullptr;
+#else
     Q.xs = L.xs;
     Q.ys = L.ys;
+#endif
     Q.S.bin_objmask = L.bin_objmask;
     Q.S.bin_shadow = L.bin_shadow;
     if (!X) {
@@ -724,7 +807,9 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
         pin_uniform(Q.dw[0], Q.dw[1], Q.dw[2], Q.dof0[2]);
         pin_uniform(Q.aa0[0], Q.aa0[1], Q.aa0[2], Q.S.ambient[0]);
         pin_uniform(Q.height, Q.S.bins_x, Q.S.bins_on, Q.ncols);
+#if !RTX_RAY_TABLE
         pin_uniform64(Q.xs, Q.ys);
+#endif
         pin_uniform64(Q.S.bin_objmask, Q.S.bin_shadow);
     }
     float* fbp = frame_fb(L);
@@ -752,8 +837,13 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
     for (int sub = 0; sub < RTX_PPL; ++sub) {
 #if RTX_TILE_SCHED && defined(__HIP_DEVICE_COMPILE__)
         const PixelRC px = pixel_rc<B>(ncols, sub, L.perm, L.xcd, L.tperm ? Pp->tile_perm : nullptr, &tile);
+#elif RTX_WAVE_HEAD && RTX_RAY_TABLE
+        const PixelRC px = px_early;
 #else
         const PixelRC px = pixel_rc<B>(ncols, sub, L.perm, L.xcd);
+#endif
+#if RTX_WAVE_HEAD && RTX_RAY_TABLE && RTX_TILE_SCHED
+        tdir = table_dir(px);
 #endif
         const bool active = px.r < L.nrows && px.c < ncols;
         any_active = any_active || active;
@@ -764,9 +854,15 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
         if (!X && bin >= 0) Q.S.tile_objmask = Q.S.bin_objmask[wave_uniform(bin)];
 #endif
         // render_pixel's image row is row0 + rr: pass the image row of px.r as that sum
+#if RTX_WAVE_HEAD && RTX_RAY_TABLE
+        if (active)
+            render_pixel<MESH, SEC, X, COUNT, JIT>(P, fbp, image_row(L, px.r) - px.r, px.r, px.c, tl, fs, hs, bin,
+                                                   tb, &tdir);
+#else
         if (active)
             render_pixel<MESH, SEC, X, COUNT, JIT>(P, fbp, image_row(L, px.r) - px.r, px.r, px.c, tl, fs, hs, bin,
                                                    tb);
+#endif
     }
     flush_tally<COUNT>(tl, L.counters, any_active);
 #if RTX_TILE_SCHED && defined(__HIP_DEVICE_COMPILE__)
@@ -833,8 +929,7 @@ __device__ __forceinline__ void render_block_spp(const KParams* __restrict__ Pp,
             int kt, ka;
             const int da = udiv_small(s, nt, rT, kt);
             const int kd = udiv_small(da, na, rA, ka);
-            const f3 focal = pixel_focal(P, cc, j);
-            const f3 ddir = normalize(sub(focal, ld3(P.dof_o + 3 * kd)));  // scene.py:58
+            const f3 ddir = primary_dir(P, cc, j, kd);  // scene.py:58
             const f3 o = sample_origin<JIT>(P, cc, j, kd, ka);
             c = cast_ray<MESH, SEC, X, COUNT>(P.S, o, ddir, P.times[tb + kt], tl, fs, hs);
         }
@@ -989,7 +1084,7 @@ __device__ __forceinline__ void first_hit(const KParams& P, int32_t row0, int32_
     f.bin = RTX_TILE == 1 ? primary_bin(P.S, row0 + (f.px.r & ~7), f.px.c & ~7) : -1;
     const int j = P.height - 1 - (row0 + f.px.r);  // reference row index (y grows upward)
     f.o = sample_origin<JIT>(P, f.px.c, j, 0, 0);
-    f.d = normalize(sub(pixel_focal(P, f.px.c, j), ld3(P.dof_o)));  // scene.py:58
+    f.d = primary_dir(P, f.px.c, j);  // scene.py:58
     f.time = P.times[tbase];
     f.h = closest_hit<MESH, X, false>(P.S, f.o, f.d, f.time, tl, hs, f.hh, f.bin, nullptr, -1);
 }
@@ -1293,6 +1388,19 @@ __global__ __launch_bounds__(256) void k_dsg_fill(const DSRect* __restrict__ r, 
         }
     }
     cells[c] = v;
+}
+
+// Fills a camera's direction table (rtx_camera_set, once per upload, after the tables and the
+// frame parameters are on the device): one lane per slot, so a wave writes one 8x8 tile's 768
+// contiguous bytes. nslots is a whole number of tiles (ray_table_slots).
+__global__ __launch_bounds__(256) void k_ray_dirs(const KParams* __restrict__ Pp, float* __restrict__ out, int64_t nslots) {
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= nslots) return;
+    const f3 d = ray_table_entry(*Pp, s);
+    float* o = out + 3 * s;
+    o[0] = d.x;
+    o[1] = d.y;
+    o[2] = d.z;
 }
 
 // Camera uploads (rtx_api.hip pinned_upload): 16-byte words from the scene's pinned host
