@@ -313,6 +313,45 @@ int rtx_render_aov(rtx_scene* scene, int32_t row0, int32_t nrows, int32_t frame,
 int rtx_render_occlusion(rtx_scene* scene, int32_t row0, int32_t nrows, int32_t frame, uint32_t* lights_dev,
                          float* ao_dev, const float* ao_dirs, int32_t n_dirs, double ao_radius, void* hip_stream);
 
+/* Resolved feature buffers of rows [row0, row0 + nrows) of the strip (no reference counterpart):
+ * what each pixel covers over ALL its samples, so the buffers line up with the colour rtx_render
+ * stores for any camera (depth of field, motion blur, antialiasing), where rtx_render_aov
+ * describes the first sample only. The pixel's samples are visited as the render visits them
+ * (provided/scene.py:57-69): kd over the n_dof DOF origins, ka over the n_aa AA origins, kt over
+ * the n_times motion times of window `frame` (0 for a camera without a sequence), time fastest.
+ * Sample (kd, ka) has the origin and direction of the render's sample, with the jitter draw the
+ * render uses for it (scene.py:63-65); each of the S = n_dof * n_aa * n_times samples is
+ * intersected with the scene (first_intersect, scene.py:86-94). H is the number of samples that
+ * hit. Buffers are pixel-major with row 0 at the top; each may be NULL (not written), but not
+ * all five:
+ *   alpha   f32 [nrows][ncols]     fl32(H) / fl32(S): the pixel's coverage
+ *   matte   f32 [nrows][ncols]     fl32(M) / fl32(S), M the number of samples whose first hit's
+ *                                  top-level object (rtx_render_aov's `object`) is in matte_objects
+ *   depth   f32 [nrows][ncols]     (sum over the hit samples of rtx_render_aov's depth) / fl32(H);
+ *                                  +inf when H == 0. A mean over the hits.
+ *   normal  f32 [nrows][ncols][3]  (sum over the hit samples of rtx_render_aov's normal, not
+ *                                  renormalised) / fl32(S)
+ *   albedo  f32 [nrows][ncols][3]  (sum over the hit samples of rtx_render_aov's albedo) / fl32(S)
+ * normal and albedo are means over all S samples: a miss adds nothing, so they are premultiplied
+ * by the coverage like the colour, whose misses add black. Every sum is fp32, starts at +0 and
+ * is added in sample order; every division is one correctly rounded fp32 division. Each
+ * sample's values are bit-identical to the reference's for its ray. For a one-sample camera
+ * every buffer equals rtx_render_aov's as a value (a -0 component is +0 after the sum) and
+ * alpha is 1 where `object` >= 0.
+ * matte_objects is a host array of n_matte >= 1 indices of top-level objects, each in
+ * [0, n_objects) and below RTX_MATTE_MAX_OBJECTS; duplicates are allowed. It is read during the
+ * call and passed to the kernel by value as a bit set; both are ignored when matte_dev is NULL.
+ * Asynchronous on the stream; the stream-ordering and graph-capture rules are rtx_render_aov's.
+ * RTX_ERR_STATE before rtx_camera_set; RTX_ERR_INVALID for a null scene, a row range outside the
+ * image, five null buffers, a frame outside the camera's sequence, and with matte_dev: null
+ * matte_objects, n_matte < 1 or an index out of range; RTX_ERR_UNSUPPORTED for a scene with
+ * hierarchies or textures (this pass is built for flat scenes only). The arguments are checked
+ * before any HIP call. rtx_last_kernel is left as it is. */
+#define RTX_MATTE_MAX_OBJECTS 256
+int rtx_render_resolved(rtx_scene* scene, int32_t row0, int32_t nrows, int32_t frame, float* alpha_dev,
+                        float* matte_dev, float* depth_dev, float* normal_dev, float* albedo_dev,
+                        const int32_t* matte_objects, int32_t n_matte, void* hip_stream);
+
 /* Rows rtx_render_groups writes for an image of `height` rows (-1: bad arguments). */
 int32_t rtx_group_rows(int32_t height, int32_t phase, int32_t stride);
 

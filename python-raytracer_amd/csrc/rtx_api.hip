@@ -14,6 +14,9 @@
 //                 samples of an output added in order (Scene.cast_ray, scene.py:81-116)
 //   k_occlusion   one work-item per output pixel: which lights reach the first sample's hit
 //                 (scene.py:150-167) and the share of free ambient-occlusion rays from it
+//   k_resolved    one work-item per output pixel: k_render's sample loops with the first hits'
+//                 attributes summed instead of the colour (coverage, mattes, mean depth,
+//                 normal and albedo)
 //   k_to_rgb8     (v * 255.0) truncated to uint8 (main.py:33)
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -4260,6 +4263,47 @@ int rtx_render_aov(rtx_scene* s, int32_t row0, int32_t nrows, int32_t frame, flo
         hipLaunchKernelGGL((k_aov<M(), X(), J()>), dim3((unsigned)nblocks), dim3(kBlock<X()>), lds, (hipStream_t)stream,
                            kp, L);
     }, s->has_mesh, s->has_ext, s->kp.jitter != RTX_JITTER_OFF);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_render_resolved(rtx_scene* s, int32_t row0, int32_t nrows, int32_t frame, float* alpha_dev, float* matte_dev,
+                        float* depth_dev, float* normal_dev, float* albedo_dev, const int32_t* matte_objects,
+                        int32_t n_matte, void* stream) {
+    const char* const fn = "rtx_render_resolved";
+    if (int rc = check_camera(fn, s)) return rc;
+    if (int rc = check_rows(fn, s, row0, nrows)) return rc;
+    if (!alpha_dev && !matte_dev && !depth_dev && !normal_dev && !albedo_dev)
+        return fail(RTX_ERR_INVALID, "rtx_render_resolved: no buffer requested (all five pointers are null)");
+    if (int rc = check_frame(fn, s, frame)) return rc;
+    ResolvedLaunch L{alpha_dev, matte_dev, depth_dev, normal_dev, albedo_dev, row0, nrows, frame * s->kp.n_times, 0, {}};
+    if (matte_dev) {
+        if (!matte_objects || n_matte < 1)
+            return fail(RTX_ERR_INVALID, "rtx_render_resolved: the matte needs at least one object, got " +
+                                             (matte_objects ? std::to_string(n_matte) : std::string("a null array")));
+        int32_t n_top = 0;  // top-level objects: every record carries its root's ordinal
+        for (const DObj& o : s->H.objs) n_top = std::max(n_top, o.oid + 1);
+        for (int k = 0; k < n_matte; ++k) {
+            const int32_t i = matte_objects[k];
+            if (i < 0 || i >= n_top || i >= RTX_MATTE_MAX_OBJECTS)
+                return fail(RTX_ERR_INVALID, "rtx_render_resolved: matte object " + std::to_string(i) + " outside the scene's " +
+                                                 std::to_string(n_top) + " objects (a matte holds indices below " +
+                                                 std::to_string(RTX_MATTE_MAX_OBJECTS) + ")");
+            L.matte_set[i >> 5] |= 1u << (i & 31);
+        }
+    }
+    // (k_resolved is a flat-scene kernel: DESIGN.md 6ag)
+    if (s->has_ext)
+        return fail(RTX_ERR_UNSUPPORTED, "rtx_render_resolved: scenes with hierarchies or textures are not supported");
+    if (nrows == 0) return RTX_OK;
+    if (int rc = check_device(fn, s)) return rc;
+    int64_t nblocks;
+    if (int rc = tile_blocks(fn, s, nrows, nblocks)) return rc;
+    const KParams* kp = s->d_kp;
+    with_bools([&](auto M, auto J) {
+        hipLaunchKernelGGL((k_resolved<M(), J()>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0,
+                           (hipStream_t)stream, kp, L);
+    }, s->has_mesh, s->kp.jitter != RTX_JITTER_OFF);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

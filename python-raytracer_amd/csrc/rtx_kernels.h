@@ -1222,6 +1222,105 @@ __global__ __launch_bounds__(kBlock<X>) void k_occlusion(const KParams* __restri
     if (L.ao != nullptr) L.ao[p] = open;
 }
 
+// The per-call block of the resolved pass (rtx_render_resolved): rows [row0, row0 + nrows) of
+// the strip, the window of motion times P.times[tbase .. tbase + n_times), one pointer per
+// buffer ([nrows][ncols] or [nrows][ncols][3]; null: not wanted) and the matte set by value,
+// bit i = top-level object i belongs to it.
+struct ResolvedLaunch {
+    float* alpha;
+    float* matte;
+    float* depth;
+    float* normal;
+    float* albedo;
+    int32_t row0, nrows, tbase, pad;
+    uint32_t matte_set[RTX_MATTE_MAX_OBJECTS / 32];
+};
+
+// What a pixel covers, over all its samples (no reference counterpart): render_pixel's sample
+// loops (scene.py:57-69: DOF origins, AA origins, motion times, time fastest; the same rays and
+// jitter draws, the odd sample's uniforms kept from its pair's Philox block) with the first
+// hit's attributes summed where render_pixel sums the colour. The mapping is k_aov's, and so
+// are closest_hit's arguments (the tile's primary bin, no pixel-in-tile). With S samples, H of
+// them hits and M of those on an object of the matte set:
+//   alpha   fl32(H) / fl32(S)         matte   fl32(M) / fl32(S)
+//   depth   sum of k_aov's depth over the hits / fl32(H); +inf when H == 0
+//   normal, albedo   sum of k_aov's normal / albedo over the hits / fl32(S): a miss adds
+//           nothing, so they carry the coverage like the colour, whose misses add black
+// Every sum is fp32 from +0 in sample order, every quotient one correctly rounded division.
+// The surface is resolved only for normal and albedo (depth and the object come from the hit
+// record), the albedo looked up only when wanted; the sums stay in registers and each buffer
+// is stored once, a tile row as one contiguous 32 B or 96 B segment. A flat-scene kernel:
+// no hierarchy stack, no textured albedo; rtx_render_resolved refuses hierarchy/texture scenes.
+template <bool MESH, bool JIT>
+__global__ __launch_bounds__(kBlock<false>) void k_resolved(const KParams* __restrict__ Pp, const ResolvedLaunch L) {
+    const HStack hs{nullptr, kBlock<false>};  // (flat scenes: closest_hit never touches it)
+    const KParams& P = *Pp;
+    const int32_t ncols = P.ncols;
+    Tally tl = {};
+    const FirstHit f = first_pixel<false>(P, L.nrows);
+    if (!f.in) return;
+    const int32_t rr = f.px.r, cc = f.px.c;
+    const int32_t bin = RTX_TILE == 1 ? primary_bin(P.S, L.row0 + (rr & ~7), cc & ~7) : -1;
+    const int j = P.height - 1 - (L.row0 + rr);  // reference row index (y grows upward)
+    const bool want_surface = L.normal != nullptr || L.albedo != nullptr;
+    int32_t nhit = 0, nmatte = 0;
+    float depth = 0.0f;
+    f3 normal = mk(0.0f, 0.0f, 0.0f), albedo = mk(0.0f, 0.0f, 0.0f);
+    f3 jr_odd = mk(0.0f, 0.0f, 0.0f);  // the odd sample's jitter uniforms of the current pair
+    const int n_dof = P.n_dof, n_aa = P.n_aa, n_times = P.n_times;
+#pragma unroll 1
+    for (int kd = 0; kd < n_dof; ++kd) {
+        // (the focal point is recomputed per DOF sample, not kept live: render_pixel's reason)
+        int32_t cc_k = cc, j_k = j;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(cc_k), "+v"(j_k));
+#endif
+        const f3 ddir = primary_dir(P, cc_k, j_k, kd);  // scene.py:58
+#pragma unroll 1
+        for (int ka = 0; ka < n_aa; ++ka) {
+            const bool philox = JIT && P.jitter == RTX_JITTER_PHILOX;
+            const bool odd = ((kd * n_aa + ka) & 1) != 0;
+            f3 jr = jr_odd;
+            if (philox && !odd) {
+                uint32_t w[4];
+                jitter_block(P, cc, j, (kd * n_aa + ka) >> 1, w);
+                jr = jitter_rnd(w, 0);
+                jr_odd = jitter_rnd(w, 1);
+            }
+            // (two calls, each with a constant pointer: a selected one keeps jr in scratch)
+            const f3 o = philox ? sample_origin<JIT>(P, cc, j, kd, ka, &jr) : sample_origin<JIT>(P, cc, j, kd, ka);
+#pragma unroll 1
+            for (int kt = 0; kt < n_times; ++kt) {
+                const float time = P.times[L.tbase + kt];
+                const SceneView S = sample_scene<false>(P.S);
+                HHit hh;  // (hierarchy hits only: never filled here)
+                const Hit h = closest_hit<MESH, false, false>(S, o, ddir, time, tl, hs, hh, bin, nullptr, -1);
+                if (h.obj != -1) {  // (a miss adds nothing)
+                    ++nhit;
+                    if (L.matte != nullptr) {
+                        const uint32_t oid = (uint32_t)hit_oid(S, h, false);
+                        if (oid < (uint32_t)RTX_MATTE_MAX_OBJECTS && ((L.matte_set[oid >> 5] >> (oid & 31u)) & 1u))
+                            ++nmatte;
+                    }
+                    if (L.depth != nullptr) depth += h.t32;
+                    if (want_surface) {
+                        const Surface sf = resolve_hit<MESH, false>(S, h, hh, o, ddir, time);
+                        normal = add(normal, sf.normal);
+                        if (L.albedo != nullptr) albedo = add(albedo, ld3(RTX_MAT(S, sf.mat).diffuse));
+                    }
+                }
+            }
+        }
+    }
+    const float ns = (float)(n_dof * n_aa * n_times);
+    const int64_t p = (int64_t)rr * ncols + cc;
+    if (L.alpha) L.alpha[p] = (float)nhit / ns;
+    if (L.matte) L.matte[p] = (float)nmatte / ns;
+    if (L.depth) L.depth[p] = nhit == 0 ? INFINITY : depth / (float)nhit;
+    if (L.normal) put3(L.normal, p, mk(normal.x / ns, normal.y / ns, normal.z / ns));
+    if (L.albedo) put3(L.albedo, p, mk(albedo.x / ns, albedo.y / ns, albedo.z / ns));
+}
+
 // The per-call block of rtx_cast_rays: n caller-built rays as SoA fp32 [3][n] (rtx_intersect's
 // layout), the motion times by value, and the output, fp32 [n / group][3].
 struct CastLaunch {

@@ -34,6 +34,21 @@ Besides the image, the occlusion buffers of Scene.render_occlusion (no reference
 as (H, W) arrays of one .npz file: `lights` (uint32, bit i: light i reaches the pixel's first
 hit) and `ao` (float32, the share of K ambient-occlusion rays of length R that are free;
 default 16 rays, unbounded).
+
+    python -m rtx.main --infile S.json --outfile out.png --resolved res.npz [--resolved-names alpha depth ...]
+                       [--matte-objects I ...] [--rgba out_rgba.png]
+
+Besides the image, the all-sample buffers of Scene.render_resolved (no reference counterpart)
+as (H, W) or (H, W, 3) float32 arrays of one .npz file: `alpha` (the pixel's coverage), `depth`
+(the mean over the samples that hit), `normal` and `albedo` (means over all samples, so
+premultiplied by the coverage like the colour), and -- with --matte-objects, the indices of the
+scene's objects that make up the matte -- `matte` (the share of the samples that see one of
+them). Default: alpha depth normal albedo, plus matte when --matte-objects is given.
+
+--rgba FILE.png writes the frame as an RGBA PNG for compositing: its RGB bytes are exactly
+--outfile's and A is the truncated (alpha * 255). The colour is ASSOCIATED (premultiplied)
+alpha over the reference's black background: a sample that misses adds black to the pixel, so
+the frame goes over a background B as RGB + (1 - A) * B, with no multiplication of RGB by A.
 """
 import argparse
 import json
@@ -42,7 +57,9 @@ import os
 import numpy
 
 from ._native import RTX_AO_MAX_DIRS
-from .scene import AOV_NAMES
+from .scene import AOV_NAMES, RESOLVED_NAMES
+
+RESOLVED_DEFAULT = ("alpha", "depth", "normal", "albedo")
 
 
 def parse(argv=None):
@@ -72,7 +89,34 @@ def parse(argv=None):
                    help="ambient-occlusion rays per pixel, 1 .. 64 (default 16)")
     p.add_argument("--ao-radius", type=float, default=None, metavar="R",
                    help="length of the ambient-occlusion rays, > 0 (default: unbounded)")
+    p.add_argument("--resolved", type=str, default=None, metavar="FILE.npz",
+                   help="also write the all-sample buffers (Scene.render_resolved) to this .npz file")
+    p.add_argument("--resolved-names", type=str, nargs="+", default=None, metavar="NAME",
+                   help="the buffers to write (default: alpha depth normal albedo; matte with --matte-objects)")
+    p.add_argument("--matte-objects", type=int, nargs="+", default=None, metavar="I",
+                   help="indices of the scene's objects whose share of each pixel the `matte` buffer holds")
+    p.add_argument("--rgba", type=str, default=None, metavar="FILE.png",
+                   help="also write the frame as an RGBA PNG: --outfile's RGB bytes with the coverage as A "
+                        "(associated alpha over the reference's black background)")
     args = p.parse_args(argv)
+    if args.resolved is not None or args.rgba is not None:
+        if args.distributed:
+            p.error("--resolved and --rgba render on one GPU: they cannot be combined with --distributed")
+        if args.frames is not None or args.panorama is not None:
+            p.error("--resolved and --rgba write the buffers of the camera's one frame: they cannot be combined "
+                    "with --frames or --panorama")
+    if args.rgba is not None and (args.subimage is not None or args.tasks is not None):
+        p.error("--rgba writes a whole image: it cannot be combined with --subimage / --tasks")
+    if args.resolved is not None:
+        names = args.resolved_names
+        if names is not None and (len(set(names)) != len(names) or not set(names) <= set(RESOLVED_NAMES)):
+            p.error("--resolved-names takes distinct names out of: " + " ".join(RESOLVED_NAMES))
+        if names is not None and ("matte" in names) != (args.matte_objects is not None):
+            p.error("the matte buffer and --matte-objects need each other")
+        if args.matte_objects is not None and min(args.matte_objects) < 0:
+            p.error("--matte-objects takes object indices >= 0")
+    elif args.resolved_names is not None or args.matte_objects is not None:
+        p.error("--resolved-names and --matte-objects need --resolved")
     if args.occlusion is not None:
         if args.distributed:
             p.error("--occlusion renders on one GPU: it cannot be combined with --distributed")
@@ -181,6 +225,36 @@ def write_occlusion(sc, args):
     return args.occlusion
 
 
+def resolved_names(args):
+    """The buffers --resolved writes: the chosen ones, else the default set (with the matte when
+    --matte-objects names one)."""
+    if args.resolved_names is not None:
+        return tuple(args.resolved_names)
+    return RESOLVED_DEFAULT + (("matte",) if args.matte_objects is not None else ())
+
+
+def write_resolved(sc, args):
+    """The chosen all-sample buffers of the frame (or strip) as one .npz file: name -> float32
+    (H, W) or (H, W, 3) array, row 0 at the top."""
+    names = resolved_names(args)
+    kw = {}
+    if args.subimage is not None and args.tasks is not None:
+        kw = dict(subimage=args.subimage, tasks=args.tasks)
+    buffers = sc.render_resolved(names, matte=args.matte_objects, **kw)
+    with open(args.resolved, "wb") as f:  # (numpy.savez would append ".npz" to a bare name)
+        numpy.savez(f, **{n: buffers[n].cpu().numpy() for n in names})
+    return args.resolved
+
+
+def rgba_image(rgb, sc):
+    """uint8 (H, W, 4): the frame's PNG bytes ``rgb`` with the coverage as A, converted on the
+    device like the colour (rtx_fb_to_rgb8). Associated alpha: the colour already holds the
+    misses' black."""
+    from .scene import fb_to_rgb8
+    a = fb_to_rgb8(sc.render_resolved(("alpha",))["alpha"]).cpu().numpy()
+    return numpy.dstack([rgb, a])
+
+
 def render_panorama(sc, width, height):
     """The panorama's PNG bytes, uint8 (height, width, 3): panorama_rays shaded at the camera's
     motion times, converted on the device like a render (rtx_fb_to_rgb8)."""
@@ -238,10 +312,14 @@ def main(argv=None):
     else:
         rgb = full_scene.render_rgb8()  # == (rot90(render()) * 255).astype(uint8), on the device
         Image.fromarray(rgb).save(args.outfile)
+        if args.rgba is not None:
+            Image.fromarray(rgba_image(rgb, full_scene), "RGBA").save(args.rgba)
     if args.aovs is not None:
         write_aovs(full_scene, args)
     if args.occlusion is not None:
         write_occlusion(full_scene, args)
+    if args.resolved is not None:
+        write_resolved(full_scene, args)
 
 
 if __name__ == "__main__":

@@ -29,6 +29,9 @@ _AOV_VEC = ("normal", "position", "albedo")
 _AOV_INT = ("object", "material")
 # the occlusion buffers of Scene.render_occlusion (rtx_render_occlusion)
 OCCLUSION_NAMES = ("lights", "ao")
+# the all-sample buffers of Scene.render_resolved (rtx_render_resolved), in the entry's order
+RESOLVED_NAMES = ("alpha", "matte", "depth", "normal", "albedo")
+_RESOLVED_VEC = ("normal", "albedo")
 
 
 def _ptr(a, ctype):
@@ -655,6 +658,78 @@ class Scene:
                    vp(out["lights"].data_ptr() if "lights" in out else 0), vp(out["ao"].data_ptr() if "ao" in out else 0),
                    _ptr(dirs, C.c_float) if dirs is not None else None, 0 if dirs is None else int(dirs.shape[0]),
                    radius, vp(st.cuda_stream))
+        return out
+
+    # ------------------------------------------------------------------ resolved buffers
+    def _matte_indices(self, matte):
+        """``matte`` (object indices, or entries of ``objects`` matched by identity) as a
+        contiguous int32 array of indices into ``objects``."""
+        if matte is None:
+            raise ValueError('the "matte" buffer needs matte=: a non-empty sequence of objects or object indices')
+        try:
+            items = list(matte)
+        except TypeError:
+            raise ValueError("matte must be a sequence of objects or object indices") from None
+        if not items:
+            raise ValueError("matte must name at least one object")
+        n = len(self.objects)
+        idx = []
+        for m in items:
+            if isinstance(m, (int, np.integer)) and not isinstance(m, bool):
+                i = int(m)
+            else:
+                i = next((k for k, ob in enumerate(self.objects) if ob is m), None)
+                if i is None:
+                    raise ValueError("matte entry %r is neither an object index nor one of scene.objects" % (m,))
+            if not 0 <= i < n or i >= N.RTX_MATTE_MAX_OBJECTS:
+                raise ValueError("matte object %d outside the scene's %d objects (a matte holds indices below %d)"
+                                 % (i, n, N.RTX_MATTE_MAX_OBJECTS))
+            idx.append(i)
+        return np.ascontiguousarray(idx, np.int32)
+
+    def render_resolved(self, buffers=("alpha", "depth", "normal", "albedo"), matte=None, subimage=0, tasks=1, row0=0,
+                        nrows=None, windows=None, frame=0, out=None, stream=None):
+        """What each pixel covers over ALL its samples (rtx_render_resolved; no reference
+        counterpart): a dict name -> float32 CUDA tensor for the chosen ``buffers`` of image
+        rows [row0, row0 + nrows) (row 0 = top) of the strip. The samples are the render's:
+        every DOF origin, AA origin (with the render's jitter draw) and motion time, so the
+        buffers line up with the colour render_device stores, where render_aovs describes
+        the first sample only. With S samples per pixel, H of them hits:
+
+        "alpha" [nrows, W]: H / S, the coverage. "matte" [nrows, W]: the share of the samples
+        whose first hit lies on an object of ``matte`` -- a non-empty sequence of indices into
+        ``objects`` or of its entries (matched by identity; duplicates allowed, indices below
+        256); it may be asked for only with ``matte``. "depth" [nrows, W]: the mean of
+        render_aovs' depth over the hits (inf when H == 0). "normal" and "albedo"
+        [nrows, W, 3]: the sums of render_aovs' values over the hits divided by S -- a miss
+        adds nothing, so they are premultiplied by the coverage like the colour. All sums are
+        fp32 in sample order (DOF, AA, time; time fastest). For a one-sample camera the
+        buffers equal render_aovs' as values.
+
+        Flat scenes only: a scene with hierarchies or textures gets RtxError
+        (RTX_ERR_UNSUPPORTED) from the entry point.
+
+        ``windows`` / ``frame`` as in render_aovs: the motion times of window ``frame``.
+        ``out``: a dict of preallocated contiguous CUDA tensors for some or all of the names.
+        Asynchronous on ``stream`` (default: torch's current stream); never synchronises."""
+        names = _buffer_names("render_resolved", "a resolved buffer", RESOLVED_NAMES, buffers)
+        windows, frame = _window_frame(windows, frame)
+        H, W = self.vc.height, strip_columns(self.vc.width, subimage, tasks)[1]
+        row0, nrows = _row_range(H, row0, nrows)
+        # (a matte without its buffer is checked and otherwise ignored, as the entry point does)
+        idx = self._matte_indices(matte) if "matte" in names or matte is not None else None
+        if "matte" not in names:
+            idx = None
+        table = {n: ((nrows, W, 3) if n in _RESOLVED_VEC else (nrows, W), torch.float32) for n in RESOLVED_NAMES}
+        out = _out_dict(out, names, table)
+        self._set_camera(subimage, tasks, windows)
+        out = _out_alloc(out, names, table)
+        st = stream if stream is not None else torch.cuda.current_stream()
+        ptr = [C.c_void_p(out[n].data_ptr() if n in out else 0) for n in RESOLVED_NAMES]
+        if nrows > 0:  # (the tensors of an empty block have no storage to point at)
+            N.call("rtx_render_resolved", self._native.h, row0, nrows, frame, *ptr,
+                   _ptr(idx, C.c_int32) if idx is not None else None, 0 if idx is None else int(idx.size),
+                   C.c_void_p(st.cuda_stream))
         return out
 
     def render(self, subimage: int = 0, tasks: int = 1) -> np.ndarray:
