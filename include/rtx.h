@@ -352,6 +352,42 @@ int rtx_render_resolved(rtx_scene* scene, int32_t row0, int32_t nrows, int32_t f
                         float* matte_dev, float* depth_dev, float* normal_dev, float* albedo_dev,
                         const int32_t* matte_objects, int32_t n_matte, void* hip_stream);
 
+/* Ranked id-coverage buffers of rows [row0, row0 + nrows) of the strip (no reference
+ * counterpart): per pixel, the objects or materials that cover the most samples, with their
+ * exact sample counts, so that the matte of ANY object set is a lookup after one pass
+ * (Cryptomatte-style). Rows, strip, `frame`, the sample order (kd over the DOF origins, ka over
+ * the AA origins, kt over the window's motion times, time fastest), the rays and the jitter
+ * draws (for Philox jitter the block of the pair (kd * n_aa + ka) >> 1, the odd sample keeping
+ * its pair's uniforms) are rtx_render_resolved's. Each sample that hits has a key:
+ *   RTX_ID_OBJECT    rtx_render_aov's `object`, the first hit's top-level object
+ *   RTX_ID_MATERIAL  rtx_render_aov's `material` (a checkered plane has two)
+ * Per pixel a table of RTX_ID_SLOTS slots starts empty. A miss does nothing. A hit with key k:
+ * a slot that holds k counts one more; else the lowest-numbered empty slot becomes (k, 1); else
+ * `dropped` counts one more. So the table keeps the first RTX_ID_SLOTS distinct keys in sample
+ * order, with exact counts. After the last sample the filled slots are ranked by count
+ * descending, equal counts by key ascending; empty slots come last. Buffers are pixel-major
+ * with row 0 at the top; each may be NULL (not written), but not all three:
+ *   ids     i32 [nrows][ncols][ranks]  the key of rank r; -1 for an empty rank
+ *   counts  i32 [nrows][ncols][ranks]  the count of rank r; 0 for an empty rank
+ *   other   i32 [nrows][ncols]         dropped + the counts of the ranks >= `ranks`, which are
+ *                                      not written
+ * Hence sum(counts) + other == H, rtx_render_resolved's hit count, and where other == 0 the
+ * written ranks are the pixel's complete and exact id histogram: with S = n_dof * n_aa *
+ * n_times, fl32(sum of the counts whose id is in a set) / fl32(S) is rtx_render_resolved's
+ * `matte` of that set, bit for bit. Counts are integers, not coverages, to keep that exact.
+ * 1 <= ranks <= RTX_ID_SLOTS.
+ * Asynchronous on the stream; the stream-ordering and graph-capture rules are rtx_render_aov's.
+ * RTX_ERR_STATE before rtx_camera_set; RTX_ERR_INVALID for a null scene, a row range outside the
+ * image, three null buffers, a frame outside the camera's sequence, a `key` that is neither of
+ * the two values, ranks outside [1, RTX_ID_SLOTS]; RTX_ERR_UNSUPPORTED for a scene with
+ * hierarchies or textures (a flat-scene pass, as rtx_render_resolved is). nrows == 0 is RTX_OK
+ * and launches nothing. The arguments are checked before any HIP call. rtx_last_kernel is left
+ * as it is. */
+#define RTX_ID_SLOTS 8
+typedef enum rtx_id_key { RTX_ID_OBJECT = 0, RTX_ID_MATERIAL = 1 } rtx_id_key;
+int rtx_render_ids(rtx_scene* scene, int32_t row0, int32_t nrows, int32_t frame, int32_t key, int32_t ranks,
+                   int32_t* ids_dev, int32_t* counts_dev, int32_t* other_dev, void* hip_stream);
+
 /* Rows rtx_render_groups writes for an image of `height` rows (-1: bad arguments). */
 int32_t rtx_group_rows(int32_t height, int32_t phase, int32_t stride);
 

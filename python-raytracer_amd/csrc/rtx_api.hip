@@ -17,7 +17,9 @@
 //   k_resolved    one work-item per output pixel: k_render's sample loops with the first hits'
 //                 attributes summed instead of the colour (coverage, mattes, mean depth,
 //                 normal and albedo)
-//   k_to_rgb8     (v * 255.0) truncated to uint8 (main.py:33)
+//   k_ids         one work-item per output pixel: k_resolved's sample loops with the hits' object
+//                 or material keys counted in a per-lane register table, ranked by count
+//   k_to_rgb8    (v * 255.0) truncated to uint8 (main.py:33)
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
@@ -4304,6 +4306,37 @@ int rtx_render_resolved(rtx_scene* s, int32_t row0, int32_t nrows, int32_t frame
         hipLaunchKernelGGL((k_resolved<M(), J()>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0,
                            (hipStream_t)stream, kp, L);
     }, s->has_mesh, s->kp.jitter != RTX_JITTER_OFF);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_render_ids(rtx_scene* s, int32_t row0, int32_t nrows, int32_t frame, int32_t key, int32_t ranks,
+                   int32_t* ids_dev, int32_t* counts_dev, int32_t* other_dev, void* stream) {
+    const char* const fn = "rtx_render_ids";
+    if (int rc = check_camera(fn, s)) return rc;
+    if (int rc = check_rows(fn, s, row0, nrows)) return rc;
+    if (!ids_dev && !counts_dev && !other_dev)
+        return fail(RTX_ERR_INVALID, "rtx_render_ids: no buffer requested (all three pointers are null)");
+    if (int rc = check_frame(fn, s, frame)) return rc;
+    if (key != RTX_ID_OBJECT && key != RTX_ID_MATERIAL)
+        return fail(RTX_ERR_INVALID, "rtx_render_ids: key " + std::to_string(key) + " is neither RTX_ID_OBJECT (0) nor "
+                                     "RTX_ID_MATERIAL (1)");
+    if (ranks < 1 || ranks > RTX_ID_SLOTS)
+        return fail(RTX_ERR_INVALID, "rtx_render_ids: ranks " + std::to_string(ranks) + " outside [1, " +
+                                         std::to_string(RTX_ID_SLOTS) + "]");
+    // (k_ids is a flat-scene kernel, as k_resolved is: DESIGN.md 6ah)
+    if (s->has_ext)
+        return fail(RTX_ERR_UNSUPPORTED, "rtx_render_ids: scenes with hierarchies or textures are not supported");
+    if (nrows == 0) return RTX_OK;
+    if (int rc = check_device(fn, s)) return rc;
+    int64_t nblocks;
+    if (int rc = tile_blocks(fn, s, nrows, nblocks)) return rc;
+    const IdsLaunch L{ids_dev, counts_dev, other_dev, row0, nrows, frame * s->kp.n_times, ranks};
+    const KParams* kp = s->d_kp;
+    with_bools([&](auto M, auto J, auto K) {
+        hipLaunchKernelGGL((k_ids<M(), J(), K()>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0, (hipStream_t)stream,
+                           kp, L);
+    }, s->has_mesh, s->kp.jitter != RTX_JITTER_OFF, key == RTX_ID_MATERIAL);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

@@ -1321,6 +1321,191 @@ __global__ __launch_bounds__(kBlock<false>) void k_resolved(const KParams* __res
     if (L.albedo) put3(L.albedo, p, mk(albedo.x / ns, albedo.y / ns, albedo.z / ns));
 }
 
+// The per-call block of the id pass (rtx_render_ids): rows [row0, row0 + nrows) of the strip,
+// the window of motion times P.times[tbase .. tbase + n_times), one pointer per buffer (ids and
+// counts [nrows][ncols][ranks], other [nrows][ncols]; null: not wanted) and the ranks written.
+struct IdsLaunch {
+    int32_t* ids;
+    int32_t* counts;
+    int32_t* other;
+    int32_t row0, nrows, tbase, ranks;
+};
+
+// A pixel's id table: RTX_ID_SLOTS (key, count) pairs, an empty slot (-1, 0). Every index below
+// is a compile-time constant after unrolling, so the sixteen words are registers.
+struct IdTable {
+    int32_t key[RTX_ID_SLOTS];
+    int32_t cnt[RTX_ID_SLOTS];
+};
+
+// n >= 0 hit samples with key k (n == 0: nothing happens, whatever k is): the slot that holds
+// k counts them; else the lowest empty slot becomes (k, n); else they are dropped (the kernel
+// finds the dropped ones as its hit count less the slots' counts). The filled slots are a
+// prefix, so the lowest empty one is slot `fill`. The slot selects sit behind a branch that a
+// wave takes only while one of its lanes brings a new key.
+__device__ __forceinline__ void id_add(IdTable& t, int32_t& fill, int32_t k, int32_t n) {
+    bool found = n == 0;
+#pragma unroll
+    for (int i = 0; i < RTX_ID_SLOTS; ++i) {
+        const bool held = t.key[i] == k;
+        t.cnt[i] += held ? n : 0;
+        found |= held;
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_amdgcn_ballot_w64(!found) == 0) return;  // (wave-uniform)
+#endif
+    const int32_t at = found ? -1 : fill;  // the slot a new key takes (RTX_ID_SLOTS: none left)
+#pragma unroll
+    for (int i = 0; i < RTX_ID_SLOTS; ++i) {
+        const bool take = at == i;
+        t.key[i] = take ? k : t.key[i];
+        t.cnt[i] = take ? n : t.cnt[i];
+    }
+    fill += (!found && fill < RTX_ID_SLOTS) ? 1 : 0;
+}
+
+// The hit samples of a pixel reach its table as runs of equal keys: consecutive samples mostly
+// see the same object, so a sample costs a compare and a count, and the table is touched only
+// when a lane of the wave changes its key (a wave-uniform branch) and once at the end. Runs are
+// added in sample order, which keeps the table's rule -- the first RTX_ID_SLOTS distinct keys --
+// as it is stated per sample; a miss neither ends nor extends a run.
+struct IdRun {
+    int32_t key = -1, n = 0;
+};
+
+__device__ __forceinline__ void id_count(IdTable& t, int32_t& fill, IdRun& run, int32_t k) {
+    const bool same = k == run.key;
+    run.n += same ? 1 : 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_amdgcn_ballot_w64(!same) == 0) return;  // (wave-uniform)
+#endif
+    id_add(t, fill, run.key, same ? 0 : run.n);  // (the lanes that go on with their run add nothing)
+    run.key = k;
+    run.n = same ? run.n : 1;
+}
+
+// Compare-exchange of slots A and B for the ranking: count descending, equal counts by key
+// ascending, empty slots (count 0) last. One unsigned 64-bit compare of (count, ~key).
+template <int A, int B>
+__device__ __forceinline__ void id_exchange(IdTable& t) {
+    const uint64_t a = ((uint64_t)(uint32_t)t.cnt[A] << 32) | (uint32_t)~t.key[A];
+    const uint64_t b = ((uint64_t)(uint32_t)t.cnt[B] << 32) | (uint32_t)~t.key[B];
+    const bool sw = a < b;
+    const int32_t ka = t.key[A], ca = t.cnt[A];
+    t.key[A] = sw ? t.key[B] : ka;
+    t.cnt[A] = sw ? t.cnt[B] : ca;
+    t.key[B] = sw ? ka : t.key[B];
+    t.cnt[B] = sw ? ca : t.cnt[B];
+}
+
+// The eight slots in rank order: a 19-exchange, 6-layer sorting network.
+__device__ __forceinline__ void id_rank(IdTable& t) {
+    id_exchange<0, 2>(t); id_exchange<1, 3>(t); id_exchange<4, 6>(t); id_exchange<5, 7>(t);
+    id_exchange<0, 4>(t); id_exchange<1, 5>(t); id_exchange<2, 6>(t); id_exchange<3, 7>(t);
+    id_exchange<0, 1>(t); id_exchange<2, 3>(t); id_exchange<4, 5>(t); id_exchange<6, 7>(t);
+    id_exchange<2, 4>(t); id_exchange<3, 5>(t);
+    id_exchange<1, 4>(t); id_exchange<3, 6>(t);
+    id_exchange<1, 2>(t); id_exchange<3, 4>(t); id_exchange<5, 6>(t);
+}
+
+// A lane's `ranks` words of one buffer, a contiguous run: 16-byte stores when the run is 4 or
+// 8 words and the buffer is 16-byte aligned (`wide`, wave-uniform), single words otherwise.
+__device__ __forceinline__ void id_store(int32_t* out, int64_t p, int32_t ranks, bool wide,
+                                         const int32_t (&v)[RTX_ID_SLOTS]) {
+    static_assert(RTX_ID_SLOTS == 8, "the run is stored as one or two 16-byte words");
+    int32_t* const run = out + p * ranks;
+    if (wide && ranks == 8) {
+        reinterpret_cast<int4*>(run)[0] = make_int4(v[0], v[1], v[2], v[3]);
+        reinterpret_cast<int4*>(run)[1] = make_int4(v[4], v[5], v[6], v[7]);
+    } else if (wide && ranks == 4) {
+        reinterpret_cast<int4*>(run)[0] = make_int4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < RTX_ID_SLOTS; ++r)
+            if (r < ranks) run[r] = v[r];
+    }
+}
+
+// Which objects (MAT false: hit_oid, rtx_render_aov's `object`) or materials (MAT true:
+// resolve_hit's mat, its `material`) cover a pixel, over all its samples (no reference
+// counterpart). The samples, rays, jitter draws, mapping and closest_hit arguments are
+// k_resolved's, loop for loop. Each hit sample's key goes into the lane's IdTable, which keeps
+// the first RTX_ID_SLOTS distinct keys in sample order with exact counts; later keys are only
+// counted as dropped. After the last sample the slots are ranked and the first L.ranks of them
+// stored: ids (-1: an empty rank), counts (0), and other = the hits not in a written rank, so
+// sum(counts) + other is k_resolved's hit count H. The surface is resolved only for the
+// material key. A flat-scene kernel, as k_resolved is.
+template <bool MESH, bool JIT, bool MAT>
+__global__ __launch_bounds__(kBlock<false>) void k_ids(const KParams* __restrict__ Pp, const IdsLaunch L) {
+    const HStack hs{nullptr, kBlock<false>};  // (flat scenes: closest_hit never touches it)
+    const KParams& P = *Pp;
+    const int32_t ncols = P.ncols;
+    Tally tl = {};
+    const FirstHit f = first_pixel<false>(P, L.nrows);
+    if (!f.in) return;
+    const int32_t rr = f.px.r, cc = f.px.c;
+    const int32_t bin = RTX_TILE == 1 ? primary_bin(P.S, L.row0 + (rr & ~7), cc & ~7) : -1;
+    const int j = P.height - 1 - (L.row0 + rr);  // reference row index (y grows upward)
+    IdTable t;
+#pragma unroll
+    for (int i = 0; i < RTX_ID_SLOTS; ++i) {
+        t.key[i] = -1;
+        t.cnt[i] = 0;
+    }
+    int32_t nhit = 0, fill = 0;
+    IdRun run;
+    f3 jr_odd = mk(0.0f, 0.0f, 0.0f);  // the odd sample's jitter uniforms of the current pair
+    const int n_dof = P.n_dof, n_aa = P.n_aa, n_times = P.n_times;
+#pragma unroll 1
+    for (int kd = 0; kd < n_dof; ++kd) {
+        // (the focal point is recomputed per DOF sample, not kept live: render_pixel's reason)
+        int32_t cc_k = cc, j_k = j;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(cc_k), "+v"(j_k));
+#endif
+        const f3 ddir = primary_dir(P, cc_k, j_k, kd);  // scene.py:58
+#pragma unroll 1
+        for (int ka = 0; ka < n_aa; ++ka) {
+            const bool philox = JIT && P.jitter == RTX_JITTER_PHILOX;
+            const bool odd = ((kd * n_aa + ka) & 1) != 0;
+            f3 jr = jr_odd;
+            if (philox && !odd) {
+                uint32_t w[4];
+                jitter_block(P, cc, j, (kd * n_aa + ka) >> 1, w);
+                jr = jitter_rnd(w, 0);
+                jr_odd = jitter_rnd(w, 1);
+            }
+            // (two calls, each with a constant pointer: a selected one keeps jr in scratch)
+            const f3 o = philox ? sample_origin<JIT>(P, cc, j, kd, ka, &jr) : sample_origin<JIT>(P, cc, j, kd, ka);
+#pragma unroll 1
+            for (int kt = 0; kt < n_times; ++kt) {
+                const float time = P.times[L.tbase + kt];
+                const SceneView S = sample_scene<false>(P.S);
+                HHit hh;  // (hierarchy hits only: never filled here)
+                const Hit h = closest_hit<MESH, false, false>(S, o, ddir, time, tl, hs, hh, bin, nullptr, -1);
+                if (h.obj != -1) {  // (a miss does nothing)
+                    ++nhit;
+                    const int32_t k = MAT ? resolve_hit<MESH, false>(S, h, hh, o, ddir, time).mat : hit_oid(S, h, false);
+                    id_count(t, fill, run, k);
+                }
+            }
+        }
+    }
+    id_add(t, fill, run.key, run.n);  // the last run
+    id_rank(t);
+    const int64_t p = (int64_t)rr * ncols + cc;
+    const int32_t ranks = L.ranks;
+    const bool wide = ((reinterpret_cast<uintptr_t>(L.ids) | reinterpret_cast<uintptr_t>(L.counts)) & 15u) == 0;
+    if (L.ids) id_store(L.ids, p, ranks, wide, t.key);
+    if (L.counts) id_store(L.counts, p, ranks, wide, t.cnt);
+    if (L.other) {
+        int32_t written = 0;
+#pragma unroll
+        for (int r = 0; r < RTX_ID_SLOTS; ++r) written += r < ranks ? t.cnt[r] : 0;
+        L.other[p] = nhit - written;
+    }
+}
+
 // The per-call block of rtx_cast_rays: n caller-built rays as SoA fp32 [3][n] (rtx_intersect's
 // layout), the motion times by value, and the output, fp32 [n / group][3].
 struct CastLaunch {

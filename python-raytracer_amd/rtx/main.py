@@ -49,6 +49,15 @@ them). Default: alpha depth normal albedo, plus matte when --matte-objects is gi
 --outfile's and A is the truncated (alpha * 255). The colour is ASSOCIATED (premultiplied)
 alpha over the reference's black background: a sample that misses adds black to the pixel, so
 the frame goes over a background B as RGB + (1 - A) * B, with no multiplication of RGB by A.
+
+    python -m rtx.main --infile S.json --outfile out.png --ids ids.npz [--id-ranks K] [--id-key object|material]
+
+Besides the image, the ranked id-coverage buffers of Scene.render_ids (no reference counterpart)
+as one .npz file: `ids` and `counts` (int32 (H, W, K): per pixel the K objects -- or materials --
+that cover the most samples and their sample counts, -1 / 0 for an empty rank), `other` (int32
+(H, W): the hits in no written rank), `samples` (the samples per pixel, a scalar) and `names`
+(the objects' or the materials' names in index order). Default: 4 ranks, the object key. The
+matte of any set of objects is then sum(counts where ids is in the set) / samples.
 """
 import argparse
 import json
@@ -56,10 +65,11 @@ import os
 
 import numpy
 
-from ._native import RTX_AO_MAX_DIRS
-from .scene import AOV_NAMES, RESOLVED_NAMES
+from ._native import RTX_AO_MAX_DIRS, RTX_ID_SLOTS
+from .scene import AOV_NAMES, ID_NAMES, RESOLVED_NAMES
 
 RESOLVED_DEFAULT = ("alpha", "depth", "normal", "albedo")
+ID_KEYS = ("object", "material")
 
 
 def parse(argv=None):
@@ -98,7 +108,23 @@ def parse(argv=None):
     p.add_argument("--rgba", type=str, default=None, metavar="FILE.png",
                    help="also write the frame as an RGBA PNG: --outfile's RGB bytes with the coverage as A "
                         "(associated alpha over the reference's black background)")
+    p.add_argument("--ids", type=str, default=None, metavar="FILE.npz",
+                   help="also write the ranked id-coverage buffers (Scene.render_ids) to this .npz file")
+    p.add_argument("--id-ranks", type=int, default=None, metavar="K",
+                   help="ranks per pixel, 1 .. %d (default 4)" % RTX_ID_SLOTS)
+    p.add_argument("--id-key", type=str, default=None, choices=ID_KEYS,
+                   help="what a sample is counted under (default object)")
     args = p.parse_args(argv)
+    if args.ids is not None:
+        if args.distributed:
+            p.error("--ids renders on one GPU: it cannot be combined with --distributed")
+        if args.frames is not None or args.panorama is not None:
+            p.error("--ids writes the buffers of the camera's one frame: it cannot be combined with --frames or "
+                    "--panorama")
+        if args.id_ranks is not None and not 1 <= args.id_ranks <= RTX_ID_SLOTS:
+            p.error("--id-ranks takes 1 .. %d" % RTX_ID_SLOTS)
+    elif args.id_ranks is not None or args.id_key is not None:
+        p.error("--id-ranks and --id-key need --ids")
     if args.resolved is not None or args.rgba is not None:
         if args.distributed:
             p.error("--resolved and --rgba render on one GPU: they cannot be combined with --distributed")
@@ -246,6 +272,22 @@ def write_resolved(sc, args):
     return args.resolved
 
 
+def write_ids(sc, args):
+    """The ranked id-coverage buffers of the frame (or strip) as one .npz file: `ids` and `counts`
+    int32 (H, W, K), `other` int32 (H, W), row 0 at the top; `samples`, the samples per pixel;
+    `names`, the objects' (or the materials') names in index order."""
+    key = args.id_key if args.id_key is not None else "object"
+    kw = {}
+    if args.subimage is not None and args.tasks is not None:
+        kw = dict(subimage=args.subimage, tasks=args.tasks)
+    buffers = sc.render_ids(args.id_ranks if args.id_ranks is not None else 4, key, ID_NAMES, **kw)
+    named = sc.objects if key == "object" else sc.materials
+    with open(args.ids, "wb") as f:  # (numpy.savez would append ".npz" to a bare name)
+        numpy.savez(f, samples=numpy.int32(sc.samples_per_pixel), names=numpy.array([str(x.name) for x in named], dtype=str),
+                    **{n: buffers[n].cpu().numpy() for n in ID_NAMES})
+    return args.ids
+
+
 def rgba_image(rgb, sc):
     """uint8 (H, W, 4): the frame's PNG bytes ``rgb`` with the coverage as A, converted on the
     device like the colour (rtx_fb_to_rgb8). Associated alpha: the colour already holds the
@@ -320,6 +362,8 @@ def main(argv=None):
         write_occlusion(full_scene, args)
     if args.resolved is not None:
         write_resolved(full_scene, args)
+    if args.ids is not None:
+        write_ids(full_scene, args)
 
 
 if __name__ == "__main__":

@@ -32,6 +32,9 @@ OCCLUSION_NAMES = ("lights", "ao")
 # the all-sample buffers of Scene.render_resolved (rtx_render_resolved), in the entry's order
 RESOLVED_NAMES = ("alpha", "matte", "depth", "normal", "albedo")
 _RESOLVED_VEC = ("normal", "albedo")
+# the ranked id-coverage buffers of Scene.render_ids (rtx_render_ids), in the entry's order
+ID_NAMES = ("ids", "counts", "other")
+_ID_KEYS = {"object": N.RTX_ID_OBJECT, "material": N.RTX_ID_MATERIAL}
 
 
 def _ptr(a, ctype):
@@ -183,6 +186,32 @@ def _out_alloc(out, names, table):
         if out.get(n) is None:
             out[n] = torch.empty(table[n][0], dtype=table[n][1], device="cuda")
     return {n: out[n] for n in names}
+
+
+def id_matte(ids, counts, members, samples):
+    """The matte of the keys ``members`` out of Scene.render_ids' buffers: float32 [nrows, W],
+    fl32(the sum of ``counts`` where ``ids`` is in ``members``) / fl32(``samples``), in torch on the
+    tensors' device. It has the meaning of render_resolved's "matte" and equals it bit for bit
+    where "other" is 0 (every hit of the pixel is then in a written rank). ``ids`` and ``counts``:
+    int32 [nrows, W, ranks]; ``members``: a non-empty sequence of object or material indices;
+    ``samples``: the camera's samples per pixel (Scene.samples_per_pixel)."""
+    for name, t in (("ids", ids), ("counts", counts)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 3:
+            raise ValueError("%s must be an int32 tensor of shape [nrows, W, ranks]" % name)
+    if ids.shape != counts.shape or ids.device != counts.device:
+        raise ValueError("ids and counts must have one shape and one device")
+    try:
+        keys = [m for m in members]
+    except TypeError:
+        raise ValueError("members must be a sequence of indices") from None
+    if not keys or any(isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 0 for m in keys):
+        raise ValueError("members must be a non-empty sequence of indices >= 0")
+    if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or samples < 1:
+        raise ValueError("samples must be an integer >= 1, got %r" % (samples,))
+    keys = torch.tensor(sorted(set(int(m) for m in keys)), dtype=torch.int32, device=ids.device)
+    inside = (ids.unsqueeze(-1) == keys).any(dim=-1)
+    n = torch.where(inside, counts, torch.zeros_like(counts)).sum(dim=-1, dtype=torch.int32)
+    return n.to(torch.float32) / torch.tensor(float(samples), dtype=torch.float32, device=ids.device)
 
 
 def _strip_rows(H, row0, nrows, groups):
@@ -732,6 +761,59 @@ class Scene:
                    C.c_void_p(st.cuda_stream))
         return out
 
+    # ------------------------------------------------------------------ ranked id-coverage buffers
+    def render_ids(self, ranks=4, key="object", buffers=ID_NAMES, subimage=0, tasks=1, row0=0, nrows=None,
+                   windows=None, frame=0, out=None, stream=None):
+        """Which objects or materials cover each pixel, over ALL its samples (rtx_render_ids; no
+        reference counterpart): a dict name -> int32 CUDA tensor for the chosen ``buffers`` of
+        image rows [row0, row0 + nrows) (row 0 = top) of the strip. One pass gives the matte of
+        every object of the frame (`id_matte`), where render_resolved's "matte" takes one pass
+        per object set. The samples are render_resolved's. Each sample that hits has a key:
+        ``key="object"`` the index in ``objects`` (render_aovs' "object"), ``key="material"``
+        the index in ``materials`` (its "material").
+
+        A pixel keeps its first 8 distinct keys in sample order with exact sample counts, and
+        ranks them by count descending, equal counts by key ascending. "ids" [nrows, W, ranks]:
+        the key of each rank, -1 for an empty rank. "counts" [nrows, W, ranks]: its samples, 0
+        for an empty rank. "other" [nrows, W]: the hits in no written rank (keys past the
+        eighth, and ranks >= ``ranks``). So counts.sum(-1) + other is the pixel's hit count, and
+        where other == 0 the ranks are the pixel's complete id histogram. 1 <= ranks <= 8.
+
+        Flat scenes only: a scene with hierarchies or textures gets RtxError
+        (RTX_ERR_UNSUPPORTED) from the entry point.
+
+        ``windows`` / ``frame`` as in render_aovs: the motion times of window ``frame``.
+        ``out``: a dict of preallocated contiguous CUDA tensors for some or all of the names.
+        Asynchronous on ``stream`` (default: torch's current stream); never synchronises."""
+        names = _buffer_names("render_ids", "an id buffer", ID_NAMES, buffers)
+        if isinstance(ranks, bool) or not isinstance(ranks, (int, np.integer)) or not 1 <= ranks <= N.RTX_ID_SLOTS:
+            raise ValueError("ranks must be an integer in [1, %d], got %r" % (N.RTX_ID_SLOTS, ranks))
+        if not isinstance(key, str) or key not in _ID_KEYS:
+            raise ValueError("unknown id key %r (known: %s)" % (key, ", ".join(_ID_KEYS)))
+        ranks = int(ranks)
+        windows, frame = _window_frame(windows, frame)
+        H, W = self.vc.height, strip_columns(self.vc.width, subimage, tasks)[1]
+        row0, nrows = _row_range(H, row0, nrows)
+        table = dict(ids=((nrows, W, ranks), torch.int32), counts=((nrows, W, ranks), torch.int32),
+                     other=((nrows, W), torch.int32))
+        out = _out_dict(out, names, table)
+        self._set_camera(subimage, tasks, windows)
+        out = _out_alloc(out, names, table)
+        st = stream if stream is not None else torch.cuda.current_stream()
+        ptr = [C.c_void_p(out[n].data_ptr() if n in out else 0) for n in ID_NAMES]
+        if nrows > 0:  # (the tensors of an empty block have no storage to point at)
+            N.call("rtx_render_ids", self._native.h, row0, nrows, frame, _ID_KEYS[key], ranks, *ptr,
+                   C.c_void_p(st.cuda_stream))
+        return out
+
+    def id_matte(self, ids, counts, members, samples=None):
+        """`id_matte` of render_ids' object-key buffers for ``members`` as render_resolved takes
+        its ``matte``: object indices or entries of ``objects`` (matched by identity).
+        ``samples``: the samples per pixel of the pass (default: samples_per_pixel, the
+        camera's own motion times)."""
+        idx = self._matte_indices(members)
+        return id_matte(ids, counts, [int(i) for i in idx], self.samples_per_pixel if samples is None else samples)
+
     def render(self, subimage: int = 0, tasks: int = 1) -> np.ndarray:
         """scene.py:35-79 — returns float64 (strip_width, height, 3), [column, row-from-bottom]."""
         fb = self.render_device(subimage, tasks)
@@ -893,4 +975,5 @@ class Scene:
 
     @property
     def samples_per_pixel(self):
+        """AA origins x DOF origins x the camera's motion times: S of render_resolved and render_ids."""
         return self.samples * self.vc.dof_samples * len(self.vc.motion_times)
