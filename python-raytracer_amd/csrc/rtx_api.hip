@@ -86,7 +86,7 @@ enum Opt {
     OPT_SELF_SKIP, OPT_TILE_SCHED, OPT_XCD_MAP, OPT_TILE_BLOCK, OPT_PRIM_ORIGIN, OPT_SPP, OPT_SPP_MIN, OPT_JIT, OPT_JIT_BAKE, OPT_JIT_EXT,
     OPT_JIT_DUMP, OPT_JIT_IDLE_BAKED, OPT_JIT_DISK_BAKED, OPT_JIT_CACHE, OPT_JIT_FLAGS, OPT_JIT_ILP, OPT_JIT_ASYNC,
     OPT_DEV_BINS, OPT_CHUNK_MODE, OPT_BIN_LDS, OPT_JIT_CSG, OPT_CSG_RAYS, OPT_CSG_SHADE, OPT_SETUP_LOG, OPT_SHADOW_BINS,
-    OPT_UNIFORM_HIT, OPT_RAY_TABLE, OPT_RAY_TABLE_MAX_MB, OPT_COUNT
+    OPT_UNIFORM_HIT, OPT_RAY_TABLE, OPT_RAY_TABLE_MAX_MB, OPT_TILE_CLASS, OPT_COUNT
 };
 struct OptDef {
     const char* name;
@@ -131,6 +131,7 @@ constexpr OptDef kOpts[OPT_COUNT] = {
     {"uniform_hit", 1, false},                // wave-uniform hits shaded from literal records (scenes of few objects, no secondary rays)
     {"ray_table", 1, false},                  // per-camera table of primary-ray directions (one-sample, unjittered cameras; 4: secondary rays and meshes without face boxes too)
     {"ray_table_max_mb", 64, false},          // the largest table built, MiB of device memory (larger strips compute their rays)
+    {"tile_class", 1, false},                 // per-bin tile classes of cameras with shadow bins: UNSHADOWED waves shade the plane without shadow tests (0: no record)
 };
 struct OptVal {
     double v;
@@ -1231,13 +1232,14 @@ bool primary_bins(const HostScene& H, const rtx_camera_desc* c, const std::vecto
 // margin 0 (tests): no margin at all -- the table then loses shadow tests that pass
 // (tests/test_shadow_bins.py: spheres within fp32 rounding of a tile's Z).
 struct SbV { double x, y, z; };
-struct SbPlane { SbV n; double num, dperp0; };  // unit normal, the origin's signed distance, the hits' offset bound
+struct SbPlane { SbV n; double num, dperp0, nn; };  // unit normal, the origin's signed distance, the hits' offset bound, the record's |n|
 struct SbObj { SbV lo, hi, ctr; double r; uint32_t bit; int32_t sphere, always, pad; };
 struct SbLight { SbV v; int32_t point, pad; };  // position, or the direction toward the light
 constexpr int kSbPlanes = 8, kSbObjs = 32, kSbLights = 8, kSbSeen = 8, kSbPoints = 4 * kSbPlanes + 8 * kSbSeen;
 struct SbScene {
     SbV o, cu, cv, cw;
     double d, dx, dy, margin, omag;
+    double cls_rho;  // 1; 0 (tests): the tile classes' plane_self bound without its growth by rho
     int32_t W, H, bins_x, bins_y, NL, n_plane, n_obs, pad;
     uint32_t all_bits, always_bits;
     SbPlane planes[kSbPlanes];
@@ -1301,9 +1303,42 @@ RTX_HD bool sb_separated(const SbV* P, int n, const SbLight& Lt, const SbObj& q,
     return false;
 }
 
-// Bin (bx, by)'s words: out[light].
-RTX_HD void sb_bin(const SbScene& S, const float* xs, const float* ys, const uint32_t* objmask, int32_t bx, int32_t by,
-                   uint32_t* out) {
+// Tile classes (SceneView::bin_class, rtx_trace.h kTile*): what sb_bin's corner rays prove for
+// every pixel of the bin -- every primary ray the kernel can cast there lies in the padded
+// pyramid, a nonnegative combination of the unit corner directions with weights summing to at
+// least 1. Each flag is set only when proven and left clear otherwise.
+//   SKY: the object mask is empty and, for every plane, all four corners have sg d.n <= -1e-3
+//     (n the unit normal, sg the sign of the origin's side) with |num| beyond its fp32 rounding
+//     (dperp0): every ray of the bin then has sg d.n <= -1e-3, far beyond the 2^-22 |n|_1 of the
+//     fp32 dot, so the kernel's quotient num / denom is negative (or denom below its epsilon) and
+//     `valid` is false in every lane. The pixel is what a miss stores.
+//   PLANE: the object mask is empty, the scene has one plane, all four corners meet it at
+//     sg d.n >= 1e-3 with |n| sg d.n >= 2e-4 (twice closest_hit's epsilon on |denom|), |num|
+//     beyond its rounding and finite hits: every lane's test of plane 0 is valid, and nothing
+//     else can be hit.
+//   UNSHADOWED: PLANE, every light's shadow word of the bin is zero (no sphere or box can
+//     occlude; moving objects and the 17th and later of a kind keep their bits set), and for
+//     every light the plane's own test is one occluded_points / occluded skip: the kernel's
+//     pm = max_i |fl32(o + d t32)_i| stays <= plane_self[4 light + 0] (not -1) in every lane.
+//     The hit's distance from the exact hit Y of its ray on the plane is at most rho (below:
+//     the offset from the plane over the smallest corner d.n, plus the roundings of
+//     fl32(o + d t32)); Y lies in the hull of the four corner hits, where the convex
+//     max_i |Y_i| is largest at a corner: pm <= max over the corners of max_i |P_i| + rho, grown
+//     once more by 2^-22 (that + |o|_inf) for the sum's last rounding. Then occluded_points
+//     returns 0 today, for every lane, whichever way its votes fall.
+// pself: the camera's plane_self table (null: no UNSHADOWED).
+struct SbClass {
+    bool sky, plane, done;
+    double pmax;  // PLANE: the bound on pm
+};
+
+// Bin (bx, by)'s words: out[light]; cls: what the class word needs (sb_bin below).
+RTX_HD void sb_bin_words(const SbScene& S, const float* xs, const float* ys, uint32_t om, int32_t bx, int32_t by,
+                         uint32_t* out, SbClass& cls) {
+    cls.sky = om == 0u;
+    cls.plane = om == 0u && S.n_plane == 1;
+    cls.done = false;
+    cls.pmax = INFINITY;
     for (int32_t l = 0; l < S.NL; ++l) out[l] = S.all_bits;
     // the bin's corner rays
     const int32_t c0 = 8 * bx, c1 = (8 * bx + 8 < S.W ? 8 * bx + 8 : S.W) - 1;
@@ -1333,17 +1368,26 @@ RTX_HD void sb_bin(const SbScene& S, const float* xs, const float* ys, const uin
             gmin = fmin(gmin, g[q]);
             gmax = fmax(gmax, g[q]);
         }
-        if (gmax <= 0.0) continue;  // no ray of the bin meets it
+        const bool num_sure = fabs(pl.num) > pl.dperp0;  // the fp32 numerator has the exact one's sign
+        if (gmax <= 0.0) {  // no ray of the bin meets it
+            cls.sky = cls.sky && gmax <= -1e-3 && num_sure;
+            cls.plane = false;
+            continue;
+        }
+        cls.sky = false;
         if (!(gmin >= 1e-3)) return;
-        double mp = 0.0;
+        double mp = 0.0, mi = 0.0;
         for (int q = 0; q < 4; ++q) {
             const SbV p = sb_axpy(S.o, fabs(pl.num) / g[q], dir[q]);
             P[np++] = p;
             mp = fmax(mp, fabs(p.x) + fabs(p.y) + fabs(p.z));
+            mi = fmax(mi, fmax(fabs(p.x), fmax(fabs(p.y), fabs(p.z))));
         }
-        rho = fmax(rho, (pl.dperp0 + 0x1p-18 * mp) / gmin + 0x1p-20 * mp);
+        const double rk = (pl.dperp0 + 0x1p-18 * mp) / gmin + 0x1p-20 * mp;
+        rho = fmax(rho, rk);
+        cls.plane = cls.plane && num_sure && gmin * pl.nn >= 2e-4 && mp < 1e30;
+        cls.pmax = mi + S.margin * S.cls_rho * (rk + 0x1p-22 * (mi + S.omag));
     }
-    const uint32_t om = objmask[(int64_t)by * S.bins_x + bx];
     if (om) {
         // an object's hit points: the pyramid between the nearest and the farthest distance from o
         // of its box; the far cap's corners lie at tfar / cos(the pyramid's half angle), beyond
@@ -1394,14 +1438,35 @@ RTX_HD void sb_bin(const SbScene& S, const float* xs, const float* ys, const uin
         }
         out[l] = m | S.always_bits;
     }
+    cls.done = true;
+}
+
+// Bin (bx, by)'s words, out[light], and -- rec not null -- its class record {object mask, class}.
+RTX_HD void sb_bin(const SbScene& S, const float* xs, const float* ys, const uint32_t* objmask, int32_t bx, int32_t by,
+                   uint32_t* out, uint2* rec = nullptr, const float* pself = nullptr) {
+    const uint32_t om = objmask[(int64_t)by * S.bins_x + bx];
+    SbClass c;
+    sb_bin_words(S, xs, ys, om, bx, by, out, c);
+    if (rec == nullptr) return;
+    uint32_t w = 0u;
+    if (c.done && c.sky) w = kTileSky;
+    if (c.done && c.plane) {
+        w = kTilePlane;
+        bool free_ = pself != nullptr;
+        for (int32_t l = 0; l < S.NL && free_; ++l)
+            free_ = out[l] == 0u && pself[4 * l] != -1.0f && c.pmax <= (double)pself[4 * l];
+        if (free_) w |= kTileUnshadowed;
+    }
+    *rec = make_uint2(om, w);
 }
 
 __global__ __launch_bounds__(64) void k_shadow_bins(const SbScene* __restrict__ S, const float* __restrict__ xs,
                                                      const float* __restrict__ ys, const uint32_t* __restrict__ objmask,
-                                                     uint32_t* __restrict__ out) {
+                                                     uint32_t* __restrict__ out, uint2* __restrict__ rec,
+                                                     const float* __restrict__ pself) {
     const int32_t b = (int32_t)(blockIdx.x * 64 + threadIdx.x);
     if (b >= S->bins_x * S->bins_y) return;
-    sb_bin(*S, xs, ys, objmask, b % S->bins_x, b / S->bins_x, out + (int64_t)b * S->NL);
+    sb_bin(*S, xs, ys, objmask, b % S->bins_x, b / S->bins_x, out + (int64_t)b * S->NL, rec ? rec + b : nullptr, pself);
 }
 
 // The camera's SbScene; false: the camera or the scene gets no shadow bins.
@@ -1422,6 +1487,7 @@ bool shadow_bins_scene(const HostScene& H, const rtx_camera_desc* c, int32_t bin
     S.o = ldd(c->aa_origins); S.cu = ldd(c->u); S.cv = ldd(c->v); S.cw = ldd(c->w);
     S.d = c->d;
     S.margin = margin;
+    S.cls_rho = 1.0;
     S.omag = amax(S.o);
     if (!sb_fin(S.o) || !sb_fin(S.cu) || !sb_fin(S.cv) || !sb_fin(S.cw) || !std::isfinite(S.d)) return false;
     for (int32_t i = 1; i < S.W; ++i) S.dx = std::max(S.dx, (double)c->xs[i] - (double)c->xs[i - 1]);  // the widest pixel steps
@@ -1441,6 +1507,7 @@ bool shadow_bins_scene(const HostScene& H, const rtx_camera_desc* c, int32_t bin
         if (!sb_fin(n) || !sb_fin(p0) || !(nn > 0.0)) return false;
         SbPlane& pl = S.planes[k];
         pl.n = SbV{n.x / nn, n.y / nn, n.z / nn};
+        pl.nn = nn;
         pl.num = sb_dot(sb_sub(p0, S.o), pl.n);
         const double n1 = (std::fabs(n.x) + std::fabs(n.y) + std::fabs(n.z)) / nn;
         // the hit's offset from the plane: dperp0 + 2^-19 n1 |P|_1
@@ -1508,6 +1575,14 @@ bool shadow_bins_scene(const HostScene& H, const rtx_camera_desc* c, int32_t bin
         for (int32_t bx = 0; bx < S.bins_x; ++bx)
             sb_bin(S, c->xs, c->ys, objmask.data(), bx, by, smask.data() + ((size_t)by * S.bins_x + bx) * S.NL);
     return true;
+}
+
+// The class records on the host (the tests' host emulation): rec[bin], by the loop above.
+[[maybe_unused]] void tile_classes(const SbScene& S, const float* xs, const float* ys, const uint32_t* objmask,
+                                   const float* pself, uint2* rec) {
+    uint32_t words[kSbLights];
+    for (int32_t by = 0; by < S.bins_y; ++by)
+        for (int32_t bx = 0; bx < S.bins_x; ++bx) sb_bin(S, xs, ys, objmask, bx, by, words, rec + (size_t)by * S.bins_x + bx, pself);
 }
 
 // Light grids (DLGrid, rtx_trace.h): shadow rays of point lights against the scene's one
@@ -2164,6 +2239,8 @@ struct CamTables {
     bool dev_faces = false;  // the mesh's face bins are built on the device
     bool heavy = false;      // heavy tiles' chunks
     bool sbins = false;      // shadow bins
+    bool tclass = false;     // tile classes (with the shadow bins: sb_bin writes both)
+    bool tclass_dev = false; // ... filled on the device with the shadow bins (k_shadow_bins), else by bind()
     bool tsched = false;     // the measured tile schedule
     bool po = false;         // the primary rays' origin-only terms
     bool rays = false;       // the primary rays' direction table
@@ -2188,6 +2265,7 @@ struct CamTables {
     size_t host_bytes = 0;  // the staged part: what precedes the segments filled later
     size_t o_xs = 0, o_ys = 0, o_dof = 0, o_aa = 0, o_times = 0, o_noise = 0, o_bounds = 0, o_pself = 0, o_dsg = 0;
     size_t o_bstart = 0, o_bfaces = 0, o_bz = 0, o_bmask = 0, o_bheavy = 0, o_hitems = 0, o_mhits = 0, o_sbs = 0;
+    size_t o_bclass = 0;
     size_t o_bshadow = 0, o_tperm = 0, o_ttime = 0, o_kp = 0, o_rays = 0, rays_bytes = 0;
 
     // times_: camera_times(c), which the caller has for the time range
@@ -2253,6 +2331,12 @@ struct CamTables {
         sbins = bins && opt_on(OPT_SHADOW_BINS) && (!H.has_secondary || opt(OPT_SHADOW_BINS) >= 2) && !H.has_mesh &&
                 !H.has_ext && shadow_bins_scene(H, c, bins_x, 1.0, sbs);
         if (sbins) o_sbs = st.put(&sbs, sizeof(sbs));
+        // tile classes (option tile_class 0: none): one record of 8 bytes per bin beside the shadow
+        // bins, for the cameras whose kernels can read it -- one sample per pixel, primary and
+        // shadow rays only (sbins with shadow_bins 2 covers secondary rays: those get none)
+        tclass = sbins && opt_on(OPT_TILE_CLASS) && !H.has_secondary && c->n_times == 1;
+        tclass_dev = tclass && on_device;
+        if (tclass && !tclass_dev) o_bclass = st.put(nullptr, sizeof(uint2) * (size_t)sbs.bins_x * sbs.bins_y);
         slog.mark("bins", st.size());
         // the measured tile schedule (tile_schedule): identity order until measured
         tsched = opt_on(OPT_TILE_SCHED) && !H.has_ext && (H.has_secondary || H.has_mesh);
@@ -2294,6 +2378,7 @@ struct CamTables {
         }
         if (heavy) o_mhits = st.put(nullptr, sizeof(uint2) * 64 * hitems.size(), true);
         if (sbins) o_bshadow = st.put(nullptr, sizeof(uint32_t) * (size_t)sbs.bins_x * sbs.bins_y * sbs.NL, true);
+        if (tclass_dev) o_bclass = st.put(nullptr, sizeof(uint2) * (size_t)sbs.bins_x * sbs.bins_y, true);
         if (tsched) o_ttime = st.put(nullptr, sizeof(uint32_t) * nw, true);
         if (rays_dev) o_rays = st.put(nullptr, rays_bytes, true);
         slog.mark("tile schedule", st.size());
@@ -2329,6 +2414,9 @@ struct CamTables {
             k.S.bins_on = 1;
         }
         if (sbins) k.S.bin_shadow = (cptr<uint32_t>)(D + o_bshadow);
+        if (tclass) k.S.bin_class = (cptr<uint2>)(D + o_bclass);
+        if (tclass && !tclass_dev)  // (host memory: the records k_shadow_bins writes)
+            tile_classes(sbs, c->xs, c->ys, bmask.data(), pself ? pself_lim.data() : nullptr, reinterpret_cast<uint2*>(D + o_bclass));
         if (heavy) {
             k.S.bin_heavy = (cptr<int32_t>)(D + o_bheavy);
             k.S.mesh_hits = reinterpret_cast<const uint2*>(D + o_mhits);
@@ -2657,6 +2745,10 @@ bool jit_spec(const std::string& arch, const SceneView& v, const KParams& kp, co
     opts.push_back(std::string("-DRTX_PRIMARY_BINS=") + (kp.S.bins_on ? "1" : "0"));
     // (only kernels of cameras with shadow bins: the others' option lists stay as they were)
     if (kp.S.bins_on && kp.S.bin_shadow != nullptr) opts.push_back("-DRTX_SHADOW_BINS=1");
+    // (and only one-sample flat kernels of primary and shadow rays of cameras with tile classes)
+    if (!spp && !ext && !sec && !mesh && kp.S.bins_on && kp.S.bin_shadow != nullptr && kp.S.bin_class != nullptr &&
+        kp.n_dof * kp.n_aa * kp.n_times == 1 && opt_on(OPT_TILE_CLASS))
+        opts.push_back("-DRTX_TILE_CLASS=1");
     // (likewise, only kernels of cameras with a direction table: one sample, no jitter)
     if (!spp && !ext && kp.ray_dirs != nullptr && kp.n_dof * kp.n_aa * kp.n_times == 1 && kp.jitter == RTX_JITTER_OFF) {
         opts.push_back("-DRTX_RAY_TABLE=1");
@@ -3606,7 +3698,9 @@ int rtx_camera_set(rtx_scene* s, const rtx_camera_desc* c) {
         hipLaunchKernelGGL(k_shadow_bins, dim3((unsigned)((nbin + 63) / 64)), dim3(64), 0, nullptr,
                            reinterpret_cast<const SbScene*>(D + T.o_sbs), reinterpret_cast<const float*>(D + T.o_xs),
                            reinterpret_cast<const float*>(D + T.o_ys), reinterpret_cast<const uint32_t*>(D + T.o_bmask),
-                           reinterpret_cast<uint32_t*>(D + T.o_bshadow));
+                           reinterpret_cast<uint32_t*>(D + T.o_bshadow),
+                           T.tclass ? reinterpret_cast<uint2*>(D + T.o_bclass) : nullptr,  // (the class records, in the same pass)
+                           T.pself ? reinterpret_cast<const float*>(D + T.o_pself) : nullptr);
         RTX_HIP(hipGetLastError());
         RTX_HIP(hipStreamSynchronize(nullptr));
         slog.mark("shadow bins (device)");
@@ -4099,6 +4193,7 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
         L.bin_objmask = s->kp.S.bin_objmask;
         L.bin_shadow = s->kp.S.bin_shadow;
         L.ray_dirs = s->kp.ray_dirs;
+        L.bin_class = s->kp.S.bin_class;
     }
     // the heavy tiles' chunks of a tile-mapped launch, just before it (the sample-parallel
     // and split kernels pass no pixel-in-tile and walk the lists). One pass serves every

@@ -287,6 +287,42 @@ RTX_HD SceneView sample_scene(const SceneView& S0) {
     return S;
 }
 
+// Tile classes (SceneView::bin_class; rtx_api.hip sb_bin proves them per camera). One-sample
+// scene-specialized kernels of flat scenes of primary and shadow rays built with RTX_TILE_CLASS
+// (rtx_api.hip jit_spec, option tile_class) read the tile's record where the others read its
+// object mask and branch on the class word at once (render_body); the host emulation reads the
+// same record in render_pixel. A tile of class UNSHADOWED takes render_pixel_plane, which stores
+// what render_pixel stores for such a pixel and counts what it counts: closest_hit's test of
+// plane 0 (valid in every lane and the only hit), then shade_uniform<0> with occ_mask 0 -- the
+// operations of the general path on the same values, without the hit-object vote and without a
+// shadow test. (SKY tiles take the general path: ending their waves at once measured 0.4-0.5 us
+// slower on TwoSpheresPlane 1080p)
+#ifndef RTX_TILE_CLASS
+#define RTX_TILE_CLASS 0
+#endif
+template <bool COUNT>
+RTX_HD void render_pixel_plane(const KParams& P, float* fb, int32_t ncols, int32_t rr, int32_t cc, f3 o, f3 d, float time,
+                               Tally& tl, const HStack& hs) {
+    const SceneView S = sample_scene<false>(P.S);
+    if (COUNT) tl.cast[0]++;
+    const DObj ob = S.objs[0];  // simple_geometry.py:105-120 (closest_hit's plane loop, k = 0)
+    const f3 n = ld3(ob.b);
+    const float denom = dot(d, n);
+#if defined(RTX_PRIM_ORIGIN) && RTX_PRIM_ORIGIN && defined(RTX_FIXED_COUNTS)
+    const float num = P.po_pnum[0];
+#else
+    const float num = dot(sub(moved(ob, ob.a, time), o), n);
+#endif
+    const Hit h{num / denom, 0, 0};
+    HHit hh;  // (a hierarchy hit's record: never read for a plane)
+    const f3 tail = clamp01(shade_uniform<false, COUNT, 0>(S, h, hh, o, d, time, tl, hs, -1, 0));
+    const f3 colour = add(mk(0.0f, 0.0f, 0.0f), tail);
+    const int64_t p = (int64_t)rr * ncols + cc;
+    put_channel(fb, 3 * p, sample_mean(P, colour.x));
+    put_channel(fb, 3 * p + 1, sample_mean(P, colour.y));
+    put_channel(fb, 3 * p + 2, sample_mean(P, colour.z));
+}
+
 // scene.py:47-79 for pixel p of the output block (host/device: the tests-only host
 // emulation runs the same body). tb: the index in P.times of the frame's window of motion
 // times (time_base below; 0 for every camera without a sequence).
@@ -306,6 +342,18 @@ RTX_HD void render_pixel(const KParams& P, float* fb, int32_t row0, int32_t rr, 
     }
     const int j = P.height - 1 - (row0 + rr);  // reference row index (y grows upward)
     const int32_t blane = bin >= 0 ? (((row0 + rr) & 7) << 3) | (cc & 7) : -1;  // the pixel in its tile
+#if !defined(__HIP_DEVICE_COMPILE__)
+    // (the host emulation: the tile's class record, as an RTX_TILE_CLASS kernel's render_body reads it)
+    if (!MESH && !SEC && !X && bin >= 0 && P.S.bin_class != nullptr && P.n_dof * P.n_aa * P.n_times == 1) {
+        const uint32_t cls = P.S.bin_class[bin].y;
+        if (cls & kTileUnshadowed) {
+            const f3 d = P.ray_dirs != nullptr ? ld3(P.ray_dirs + 3 * (int64_t)ray_slot(row0 + rr, cc, ncols))
+                                               : primary_dir(P, cc, j, 0);
+            render_pixel_plane<COUNT>(P, fb, ncols, rr, cc, sample_origin<false>(P, cc, j, 0, 0), d, P.times[tb], tl, hs);
+            return;
+        }
+    }
+#endif
 #if defined(RTX_PRIM_ORIGIN) && RTX_PRIM_ORIGIN && defined(RTX_FIXED_COUNTS)
     OriginTerms prim;  // the primary rays' origin-only terms (host-computed)
 #pragma unroll
@@ -507,6 +555,7 @@ struct Launch {
     cptr<float> xs, ys;
     cptr<uint32_t> bin_objmask, bin_shadow;
     cptr<float> ray_dirs;  // (KParams::ray_dirs)
+    cptr<uint2> bin_class;  // (SceneView::bin_class)
 };
 
 // This block's framebuffer (frame blockIdx.y of a batched launch; the only frame otherwise).
@@ -800,6 +849,12 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
 #endif
     Q.S.bin_objmask = L.bin_objmask;
     Q.S.bin_shadow = L.bin_shadow;
+#if RTX_TILE_CLASS
+    static_assert(!MESH && !SEC && !X && RTX_TILE == 1 && RTX_PPL == 1, "tile classes: flat primary + shadow kernels");
+    cptr<uint2> bclass = L.bin_class;
+    int64_t bclass_pad = 0;  // (pinned beside it only)
+    pin_uniform64(bclass, bclass_pad);
+#endif
     if (!X) {
         pin_uniform(Q.pos[0], Q.pos[1], Q.pos[2], Q.focal);
         pin_uniform(Q.u[0], Q.u[1], Q.u[2], Q.dof0[0]);
@@ -849,7 +904,36 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
         any_active = any_active || active;
         // primary-ray face bin of the wave's 8x8 tile (its top-left pixel)
         const int32_t bin = RTX_TILE == 1 ? primary_bin(P.S, image_row(L, px.r & ~7), px.c & ~7) : -1;
-#if RTX_WAVE_HEAD && RTX_TILE == 1 && RTX_PRIMARY_BINS
+#if RTX_TILE_CLASS && RTX_WAVE_HEAD && RTX_PRIMARY_BINS
+        // the tile's record: its object mask, as below, and its class word in the same scalar
+        // load. The class is branched on at once, by scalar branches: nothing of it stays live
+        // across the general path's hit test.
+        // The load is one 64-bit word at an address that is valid whatever bin is (entry 0 for a
+        // tile off the grid: a kernel with classes has a table), so it goes out here, beside the
+        // direction table's, not behind the branch on bin and the wait for the direction.
+        uint64_t rec = reinterpret_cast<cptr<uint64_t>>(bclass)[wave_uniform(bin >= 0 ? bin : 0)];
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(rec));  // (pinned here: left to itself the load sinks to its use, below that wait)
+#endif
+        if (bin >= 0) {
+            const uint32_t cls = (uint32_t)(rec >> 32);
+            Q.S.tile_objmask = (uint32_t)rec;
+            if (cls & kTileUnshadowed) {
+                if (active) {
+                    const int32_t row0c = image_row(L, px.r) - px.r;
+#if RTX_RAY_TABLE
+                    const f3 dc = tdir;
+#else
+                    const f3 dc = primary_dir(P, px.c, P.height - 1 - (row0c + px.r), 0);
+#endif
+                    render_pixel_plane<COUNT>(P, fbp, ncols, px.r, px.c,
+                                              sample_origin<false>(P, px.c, P.height - 1 - (row0c + px.r), 0, 0), dc,
+                                              P.times[tb], tl, hs);
+                }
+                continue;
+            }
+        }
+#elif RTX_WAVE_HEAD && RTX_TILE == 1 && RTX_PRIMARY_BINS
         // the tile's object mask, fetched here and handed down by value (SceneView::tile_objmask)
         if (!X && bin >= 0) Q.S.tile_objmask = Q.S.bin_objmask[wave_uniform(bin)];
 #endif

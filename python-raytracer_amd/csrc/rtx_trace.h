@@ -377,8 +377,19 @@ struct SceneView {
     // One-sample scene-specialized kernels (rtx_kernels.h render_body, RTX_WAVE_HEAD): the
     // wave's tile's word of bin_objmask, read at the top of the kernel and handed down by
     // value; zero in memory
-    uint32_t tile_objmask, pad14, pad15, pad16;
+    uint32_t tile_objmask, pad14;
+    // Tile classes (per camera; rtx_api.hip sb_bin): per bin one aligned record {the bin's word
+    // of bin_objmask, class word of kTile* flags}, each flag proven for every pixel of the
+    // bin; null: the camera has none (kernels built with RTX_TILE_CLASS read the record where
+    // the others read the mask word)
+    cptr<uint2> bin_class;
 };
+
+// The class word's flags. SKY: no ray of the tile hits anything. PLANE: every ray hits plane 0
+// (the scene's only one) and nothing else. UNSHADOWED: PLANE, and no light's shadow ray from any
+// of the tile's hit points is occluded (every shadow-bin word is empty and the plane's own
+// test is one plane_self skips).
+constexpr uint32_t kTileSky = 1u, kTilePlane = 2u, kTileUnshadowed = 4u;
 
 // Kernels whose render_body takes the frame parameters by value at its top (rtx_kernels.h): the
 // one-sample scene-specialized ones. Multi-sample kernels re-read them per sample on purpose
@@ -3114,15 +3125,18 @@ RTX_HD DMat select_mat(bool second, const DMat& a, const DMat& b) {
 }
 // regular_lighting of a camera ray's hit h on flat object K (not a mesh), which every live
 // lane of the wave hit: cast_ray's resolve_hit, material and lighting with K for h.obj.
+// occ_mask 0 (tiles of class UNSHADOWED, rtx_kernels.h render_pixel_plane): no shadow ray is
+// traced, regular_lighting's meaning of it.
 template <bool MESH, bool COUNT, int K>
 RTX_HD f3 shade_uniform(const SceneView& S, const Hit& h, const HHit& hh, f3 o, f3 d, float time, Tally& tl,
-                        const HStack& hs, int32_t bin) {
+                        const HStack& hs, int32_t bin, int64_t occ_mask = -1) {
     const Surface sf = resolve_hit<MESH, false, K>(S, h, hh, o, d, time);
     // Surface::mat is the object's first material, or one of a checker plane's two
     const DObj ob = RTX_OBJ(S, K);
     const DMat m0 = RTX_MAT(S, ob.mat0);
     const DMat m = (ob.type != OBJ_PLANE || ob.nmat == 1) ? m0 : select_mat(sf.mat == ob.mat1, m0, RTX_MAT(S, ob.mat1));
-    return regular_lighting<MESH, false, COUNT>(S, d, sf.position, sf.normal, m, ld3(m.diffuse), time, tl, hs, -1, K, bin);
+    return regular_lighting<MESH, false, COUNT>(S, d, sf.position, sf.normal, m, ld3(m.diffuse), time, tl, hs, occ_mask, K,
+                                                bin);
 }
 
 template <bool MESH, bool SEC, bool X, bool COUNT>
