@@ -388,6 +388,40 @@ typedef enum rtx_id_key { RTX_ID_OBJECT = 0, RTX_ID_MATERIAL = 1 } rtx_id_key;
 int rtx_render_ids(rtx_scene* scene, int32_t row0, int32_t nrows, int32_t frame, int32_t key, int32_t ranks,
                    int32_t* ids_dev, int32_t* counts_dev, int32_t* other_dev, void* hip_stream);
 
+/* Light groups of rows [row0, row0 + nrows) of the strip (no reference counterpart): the colour
+ * rtx_render stores, separated by light set, in one pass. out_dev is f32
+ * [n_groups][nrows][ncols][3]; each plane has the framebuffer's layout (row 0 at the top), so
+ * rtx_fb_to_rgb8 applies to a plane. Plane g holds, bit for bit, what rtx_render stores for
+ * those rows with the motion times of window `frame` (0 for a camera without a sequence) for the
+ * scene with two changes: its lights are exactly those with light_group[li] == g, in their
+ * original order, and its ambient is the scene's when ambient_group == g, else (0, 0, 0).
+ * Everything else is rtx_render's: the samples and their order (DOF origins, AA origins, motion
+ * times, time fastest), the jitter draws, the per-level clamp of provided/scene.py:113-115, the
+ * fp32 sums from +0 and the one division by fl32(S) per channel.
+ *   light_group    host array of n_lights entries, read during the call and passed to the kernel
+ *                  by value: the group of light li in [0, n_groups), or -1 for a light that
+ *                  belongs to no group and lights nothing (its shadow rays are not traced).
+ *   n_groups       1 <= n_groups <= RTX_LIGHT_GROUPS_MAX. A group may be empty: its plane is
+ *                  black, or the ambient term alone.
+ *   ambient_group  the group that receives the scene's ambient term, or -1 for none.
+ * Every ray chain is traced once and every light's shadow ray once per chain level, whatever
+ * the grouping (no ray of the renderer depends on a light); only the shading is per group.
+ * With n_groups == 1, every light in group 0 and ambient_group == 0 the plane equals
+ * rtx_render's framebuffer bit for bit. The planes are clamped per chain level, as the
+ * reference clamps: their sum equals the beauty image only where no clamp engages, and then
+ * only up to fp32 rounding -- the sum is documented, not guaranteed.
+ * Asynchronous on the stream; the stream-ordering and graph-capture rules are rtx_render_aov's.
+ * RTX_ERR_STATE before rtx_camera_set; RTX_ERR_INVALID for a null scene, a row range outside the
+ * image, a null out_dev, a frame outside the camera's sequence, a null light_group, n_groups
+ * outside [1, RTX_LIGHT_GROUPS_MAX], a scene with more than 32 lights, a light_group entry or
+ * ambient_group outside [-1, n_groups); RTX_ERR_UNSUPPORTED for a scene with hierarchies or
+ * textures (a flat-scene pass, as rtx_render_resolved is). nrows == 0 is RTX_OK and launches
+ * nothing; a scene without lights is valid. The arguments are checked before any HIP call.
+ * rtx_last_kernel is left as it is; the call writes no counters. */
+#define RTX_LIGHT_GROUPS_MAX 8
+int rtx_render_light_groups(rtx_scene* scene, int32_t row0, int32_t nrows, int32_t frame, const int32_t* light_group,
+                            int32_t n_groups, int32_t ambient_group, float* out_dev, void* hip_stream);
+
 /* Rows rtx_render_groups writes for an image of `height` rows (-1: bad arguments). */
 int32_t rtx_group_rows(int32_t height, int32_t phase, int32_t stride);
 

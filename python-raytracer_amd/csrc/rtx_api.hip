@@ -19,6 +19,8 @@
 //                 normal and albedo)
 //   k_ids         one work-item per output pixel: k_resolved's sample loops with the hits' object
 //                 or material keys counted in a per-lane register table, ranked by count
+//   k_light_groups  one work-item per output pixel: k_render's sample loops with one colour per
+//                 light group (rtx_light_groups.h: one trace, one shadow test per light and level)
 //   k_to_rgb8    (v * 255.0) truncated to uint8 (main.py:33)
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
@@ -47,6 +49,7 @@
 #include "rtx_bins.h"
 #include "rtx_launch.h"
 #include "rtx_split.h"
+#include "rtx_light_groups.h"
 
 // faces per mesh BVH leaf (cluster); meshes of at most kFaceCullMaxFaces faces also
 // test each face's box before its exact test (DObj::face_cull)
@@ -4432,6 +4435,52 @@ int rtx_render_ids(rtx_scene* s, int32_t row0, int32_t nrows, int32_t frame, int
         hipLaunchKernelGGL((k_ids<M(), J(), K()>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0, (hipStream_t)stream,
                            kp, L);
     }, s->has_mesh, s->kp.jitter != RTX_JITTER_OFF, key == RTX_ID_MATERIAL);
+    RTX_HIP(hipGetLastError());
+    return RTX_OK;
+}
+
+int rtx_render_light_groups(rtx_scene* s, int32_t row0, int32_t nrows, int32_t frame, const int32_t* light_group,
+                            int32_t n_groups, int32_t ambient_group, float* out_dev, void* stream) {
+    const char* const fn = "rtx_render_light_groups";
+    if (int rc = check_camera(fn, s)) return rc;
+    if (int rc = check_rows(fn, s, row0, nrows)) return rc;
+    if (!out_dev) return fail(RTX_ERR_INVALID, "rtx_render_light_groups: null output buffer");
+    if (int rc = check_frame(fn, s, frame)) return rc;
+    if (!light_group) return fail(RTX_ERR_INVALID, "rtx_render_light_groups: null light_group");
+    if (n_groups < 1 || n_groups > RTX_LIGHT_GROUPS_MAX)
+        return fail(RTX_ERR_INVALID, "rtx_render_light_groups: n_groups " + std::to_string(n_groups) + " outside [1, " +
+                                         std::to_string(RTX_LIGHT_GROUPS_MAX) + "]");
+    const int32_t n_lights = s->view.n_lights;
+    if (n_lights > 32)  // (the word of free lights a chain level records)
+        return fail(RTX_ERR_INVALID, "rtx_render_light_groups: the pass holds 32 lights, the scene has " +
+                                         std::to_string(n_lights));
+    LightGroupsLaunch L{out_dev, (int64_t)nrows * s->kp.ncols * 3, row0, nrows, frame * s->kp.n_times, n_groups,
+                        ambient_group, 0u, ~0ull, ~0ull};
+    for (int32_t li = 0; li < n_lights; ++li) {
+        const int32_t g = light_group[li];
+        if (g < -1 || g >= n_groups)
+            return fail(RTX_ERR_INVALID, "rtx_render_light_groups: light " + std::to_string(li) + " has group " +
+                                             std::to_string(g) + " outside [-1, " + std::to_string(n_groups) + ")");
+        if (g < 0) continue;
+        uint64_t& w = li < 16 ? L.grp_lo : L.grp_hi;
+        w = (w & ~(15ull << ((li & 15) * 4))) | ((uint64_t)g << ((li & 15) * 4));
+        L.used |= 1u << li;
+    }
+    if (ambient_group < -1 || ambient_group >= n_groups)
+        return fail(RTX_ERR_INVALID, "rtx_render_light_groups: ambient_group " + std::to_string(ambient_group) +
+                                         " outside [-1, " + std::to_string(n_groups) + ")");
+    // (k_light_groups is a flat-scene kernel, as k_resolved is: DESIGN.md 6aj)
+    if (s->has_ext)
+        return fail(RTX_ERR_UNSUPPORTED, "rtx_render_light_groups: scenes with hierarchies or textures are not supported");
+    if (nrows == 0) return RTX_OK;
+    if (int rc = check_device(fn, s)) return rc;
+    int64_t nblocks;
+    if (int rc = tile_blocks(fn, s, nrows, nblocks)) return rc;
+    const KParams* kp = s->d_kp;
+    with_bools([&](auto M, auto S, auto J, auto W) {
+        hipLaunchKernelGGL((k_light_groups<M(), S(), J(), W() ? 8 : 4>), dim3((unsigned)nblocks), dim3(kBlock<false>), 0,
+                           (hipStream_t)stream, kp, L);
+    }, s->has_mesh, s->has_secondary, s->kp.jitter != RTX_JITTER_OFF, n_groups > 4);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

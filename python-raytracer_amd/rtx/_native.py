@@ -32,6 +32,7 @@ RTX_AO_MAX_DIRS = 64  # ambient-occlusion directions of one rtx_render_occlusion
 RTX_MATTE_MAX_OBJECTS = 256  # object indices a matte of rtx_render_resolved can hold
 RTX_ID_SLOTS = 8  # slots of a pixel's id table, and the most ranks rtx_render_ids writes
 RTX_ID_OBJECT, RTX_ID_MATERIAL = 0, 1
+RTX_LIGHT_GROUPS_MAX = 8  # planes of one rtx_render_light_groups call
 
 _f3 = C.c_float * 3
 
@@ -97,7 +98,8 @@ EXPORTS = ["rtx_abi_version", "rtx_last_error", "rtx_scene_create", "rtx_scene_d
            "rtx_render_rgb8", "rtx_render_groups_rgb8", "rtx_last_kernel", "rtx_render_frames",
            "rtx_render_groups_frames", "rtx_jit_modules", "rtx_set_option", "rtx_get_option", "rtx_option_name",
            "rtx_graph_launch", "rtx_jit_wait", "rtx_render_sequence", "rtx_render_groups_sequence",
-           "rtx_render_aov", "rtx_cast_rays", "rtx_render_occlusion", "rtx_render_resolved", "rtx_render_ids"]
+           "rtx_render_aov", "rtx_cast_rays", "rtx_render_occlusion", "rtx_render_resolved", "rtx_render_ids",
+           "rtx_render_light_groups"]
 
 
 def load():
@@ -138,6 +140,9 @@ def load():
                                                 C.POINTER(C.c_int32), C.c_int32, vp]
         if hasattr(lib, "rtx_render_ids"):
             lib.rtx_render_ids.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        if hasattr(lib, "rtx_render_light_groups"):
+            lib.rtx_render_light_groups.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                                    C.c_int32, vp, vp]
         lib.rtx_group_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.rtx_group_rows.restype = C.c_int32
         lib.rtx_intersect.argtypes = [vp, C.c_int64, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]

@@ -214,6 +214,51 @@ def id_matte(ids, counts, members, samples):
     return n.to(torch.float32) / torch.tensor(float(samples), dtype=torch.float32, device=ids.device)
 
 
+def light_group_table(n_lights, groups=None, ambient="own"):
+    """The arguments of Scene.render_light_groups as rtx_render_light_groups takes them:
+    (light_group, n_groups, ambient_group), with light_group an int32 array of ``n_lights``
+    entries -- light li's group, or -1 for a light in no group, which lights nothing.
+
+    ``groups``: a sequence of sequences of light indices, group g = groups[g] (a group may be
+    empty); None: one group per light, in light order. ``ambient``: "own" (a group of its own,
+    appended last), the index of one of ``groups``, or None (the ambient term is dropped).
+    ValueError for a light index out of range, a light in two groups, an ambient that is none
+    of the three, or more than 8 groups once the ambient's is counted (and for none at all)."""
+    n_lights = int(n_lights)
+    if groups is None:
+        groups = [[li] for li in range(n_lights)]
+    try:
+        groups = [list(g) for g in groups]
+    except TypeError:
+        raise ValueError("groups must be a sequence of sequences of light indices") from None
+    table = np.full(n_lights, -1, np.int32)
+    for g, members in enumerate(groups):
+        for li in members:
+            if isinstance(li, bool) or not isinstance(li, (int, np.integer)) or not 0 <= li < n_lights:
+                raise ValueError("light %r of group %d outside the scene's %d lights" % (li, g, n_lights))
+            if table[li] >= 0:
+                raise ValueError("light %d is in two groups: %d and %d" % (li, table[li], g))
+            table[li] = g
+    n_groups = len(groups)
+    if ambient is None:
+        ambient_group = -1
+    elif isinstance(ambient, str):
+        if ambient != "own":
+            raise ValueError('ambient must be "own", a group index or None, got %r' % (ambient,))
+        ambient_group = n_groups
+        n_groups += 1
+    elif isinstance(ambient, bool) or not isinstance(ambient, (int, np.integer)):
+        raise ValueError('ambient must be "own", a group index or None, got %r' % (ambient,))
+    elif not 0 <= ambient < n_groups:
+        raise ValueError("ambient group %d outside the %d groups" % (ambient, n_groups))
+    else:
+        ambient_group = int(ambient)
+    if not 1 <= n_groups <= N.RTX_LIGHT_GROUPS_MAX:
+        raise ValueError("a light-group pass holds 1 to %d groups (the ambient's own included), got %d"
+                         % (N.RTX_LIGHT_GROUPS_MAX, n_groups))
+    return table, n_groups, ambient_group
+
+
 def _strip_rows(H, row0, nrows, groups):
     """The row count of a render: of ``groups=(k, n)`` when given, else nrows (None: the rest)."""
     if groups is not None:
@@ -804,6 +849,48 @@ class Scene:
         if nrows > 0:  # (the tensors of an empty block have no storage to point at)
             N.call("rtx_render_ids", self._native.h, row0, nrows, frame, _ID_KEYS[key], ranks, *ptr,
                    C.c_void_p(st.cuda_stream))
+        return out
+
+    # ------------------------------------------------------------------ light groups
+    def render_light_groups(self, groups=None, ambient="own", subimage=0, tasks=1, row0=0, nrows=None, windows=None,
+                            frame=0, out=None, stream=None):
+        """The colour render_device stores, separated by light set, in one pass
+        (rtx_render_light_groups; no reference counterpart): a float32 CUDA tensor
+        [G, nrows, W, 3] for image rows [row0, row0 + nrows) (row 0 = top) of the strip.
+        Plane g is, bit for bit, render_device's image of this scene with only the lights of
+        ``groups[g]`` (in their order) and, unless g is the ambient's group, a zero ambient.
+
+        ``groups``: a sequence of sequences of indices into ``lights`` (None: one group per
+        light); a light in no group lights nothing. ``ambient``: "own" (a group appended last),
+        a group index, or None (dropped). At most 8 groups, the ambient's own included, and at
+        most 32 lights. The ray chains and shadow rays are traced once, whatever the grouping.
+        The planes are clamped per chain level like the image, so they sum to it only where no
+        clamp engages (and then up to fp32 rounding).
+
+        Flat scenes only: a scene with hierarchies or textures gets RtxError
+        (RTX_ERR_UNSUPPORTED) from the entry point.
+
+        ``windows`` / ``frame`` as in render_aovs: the motion times of window ``frame``.
+        ``out``: a preallocated contiguous float32 CUDA tensor [G, nrows, W, 3].
+        Asynchronous on ``stream`` (default: torch's current stream); never synchronises."""
+        table, n_groups, ambient_group = light_group_table(len(self.lights), groups, ambient)
+        if len(self.lights) > 32:
+            raise ValueError("a light-group pass holds 32 lights, the scene has %d" % len(self.lights))
+        windows, frame = _window_frame(windows, frame)
+        H, W = self.vc.height, strip_columns(self.vc.width, subimage, tasks)[1]
+        row0, nrows = _row_range(H, row0, nrows)
+        shape = (n_groups, nrows, W, 3)
+        if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape
+                                or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of shape %s" % (shape,))
+        self._set_camera(subimage, tasks, windows)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device="cuda")
+        st = stream if stream is not None else torch.cuda.current_stream()
+        if nrows > 0:  # (the tensor of an empty block has no storage to point at)
+            arg = table if table.size else np.full(1, -1, np.int32)  # (never a null pointer: no lights)
+            N.call("rtx_render_light_groups", self._native.h, row0, nrows, frame, _ptr(arg, C.c_int32), n_groups,
+                   ambient_group, C.c_void_p(out.data_ptr()), C.c_void_p(st.cuda_stream))
         return out
 
     def id_matte(self, ids, counts, members, samples=None):
