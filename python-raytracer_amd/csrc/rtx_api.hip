@@ -4197,6 +4197,8 @@ int render_launch(rtx_scene* s, Launch L, uint64_t* counters_dev, void* stream, 
         L.bin_shadow = s->kp.S.bin_shadow;
         L.ray_dirs = s->kp.ray_dirs;
         L.bin_class = s->kp.S.bin_class;
+        L.bins_x = s->kp.S.bins_x;
+        L.bins_on = s->kp.S.bins_on;
     }
     // the heavy tiles' chunks of a tile-mapped launch, just before it (the sample-parallel
     // and split kernels pass no pixel-in-tile and walk the lists). One pass serves every

@@ -556,6 +556,11 @@ struct Launch {
     cptr<uint32_t> bin_objmask, bin_shadow;
     cptr<float> ray_dirs;  // (KParams::ray_dirs)
     cptr<uint2> bin_class;  // (SceneView::bin_class)
+    // SceneView::bins_x / bins_on of the current camera: a kernel with a direction table and no
+    // tile schedule addresses its tile's record from the arguments alone and takes the bins'
+    // grid from here, not from KParams. Every launcher of render_body fills them with the
+    // tables above (render_launch, the only one).
+    int32_t bins_x, bins_on;
 };
 
 // This block's framebuffer (frame blockIdx.y of a batched launch; the only frame otherwise).
@@ -770,6 +775,14 @@ __device__ __forceinline__ void pin_uniform(T& a, T& b, T& c, T& d) {
     d = __builtin_bit_cast(T, w3);
 }
 
+template <class T>  // (one of them)
+__device__ __forceinline__ void pin_uniform(T& a) {
+    static_assert(sizeof(T) == 4, "32-bit scalar");
+    uint32_t w0 = __builtin_bit_cast(uint32_t, a);
+    asm volatile("" : "+s"(w0));
+    a = __builtin_bit_cast(T, w0);
+}
+
 template <class A, class B>  // (two wave-uniform pointers or 64-bit words)
 __device__ __forceinline__ void pin_uniform64(A& a, B& b) {
     static_assert(sizeof(A) == 8 && sizeof(B) == 8, "64-bit scalars");
@@ -805,7 +818,7 @@ struct WaveClock {
 #endif
 
 template <bool MESH, bool SEC, bool X, bool COUNT, bool JIT>
-__device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, const Launch L) {
+__device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, const Launch L0) {
     constexpr int B = kBlock<X>;
     RTX_WAVE_CLOCK_BEGIN
     if (MESH) stage_mesh_lds(Pp->S);
@@ -822,6 +835,60 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
     // its own basic block, behind the previous one's wait). What stood behind a pointer of
     // KParams comes from the camera block (dof0 / aa0: the only origins of a one-sample
     // camera) or is addressed from Launch's copies of the table pointers.
+#if RTX_RAY_TABLE && !RTX_TILE_SCHED
+    // A kernel with a direction table and no tile schedule knows its tile from its ids: what its
+    // two table loads are addressed from -- the direction table, the tile records, the launch's
+    // rows and the bins' grid (Launch's copies of SceneView's) -- is all of it kernel arguments,
+    // pinned with the camera block's words, so every scalar load the path to the hit needs is
+    // in flight before the wave's first scalar wait and the table loads issue behind that wait
+    // (DESIGN.md 6ak). Kernels with a tile schedule learn their tile from a dependent load and
+    // keep the form below, as do kernels without a table.
+    static_assert(!X && RTX_TILE == 1 && RTX_PPL == 1, "one 8x8 tile per wave");
+    Launch L = L0;
+    KParams Q = *Pp;
+    Q.S.bins_x = L.bins_x;
+    Q.S.bins_on = L.bins_on;
+    Q.xs = nullptr;  // (never read: the table stands for both)
+    Q.ys = nullptr;
+    Q.S.bin_objmask = L.bin_objmask;
+    Q.S.bin_shadow = L.bin_shadow;
+    pin_uniform64(L.ray_dirs, L.bin_class);
+    pin_uniform(L.row0, L.nrows, L.gphase, L.gstride);
+    // (The table stands for the camera's basis as well: pos, u, v, dw, focal and dof0 are never
+    // read and not pinned. Groups are pinned whole, pad words included: a word of a load in
+    // flight that nothing reads is a register the next load may be given, and that load then
+    // waits for the first.)
+    pin_uniform(Q.aa0[0], Q.aa0[1], Q.aa0[2], Q.aa0[3]);
+    pin_uniform(Q.S.ambient[0], Q.S.ambient[1], Q.S.ambient[2], Q.S.ambient[3]);
+    pin_uniform(Q.height, Q.S.bins_x, Q.S.bins_on, Q.ncols);
+#if defined(RTX_PRIM_ORIGIN) && RTX_PRIM_ORIGIN && defined(RTX_FIXED_COUNTS)
+    // (the hit tests' origin-only terms: render_pixel and render_pixel_plane read them)
+#pragma unroll
+    for (int k = 0; k < RTX_FIXED_NP; ++k) pin_uniform(Q.po_pnum[k]);
+#pragma unroll
+    for (int k = 0; k < RTX_FIXED_NS; ++k) pin_uniform(Q.po_soc[k][0], Q.po_soc[k][1], Q.po_soc[k][2], Q.po_sq[k]);
+#endif
+    pin_uniform64(Q.S.bin_objmask, Q.S.bin_shadow);
+    float* fbp = frame_fb(L);
+    int64_t fbw = L.fstride;  // (pinned beside it only)
+    pin_uniform64(fbp, fbw);
+    // The pixel's direction from the camera's table. The row is held inside the launch's rows:
+    // lanes below a ragged bottom edge, and waves past the last tile, read an entry of the
+    // last row (the columns of a ragged right tile have slots of their own).
+    const cptr<float> tdirs = L.ray_dirs;
+    auto table_dir = [&](const PixelRC& px) {
+        const int32_t rq = px.r < L.nrows ? px.r : L.nrows - 1;
+        return ld3(tdirs + 3u * ray_slot(image_row(L, rq), px.c, ncols));
+    };
+    f3 tdir = mk(0.0f, 0.0f, 0.0f);
+    const PixelRC px_early = pixel_rc<B>(ncols, 0, L.perm, L.xcd);
+    tdir = table_dir(px_early);
+#if RTX_TILE_CLASS
+    static_assert(!MESH && !SEC && !X && RTX_TILE == 1 && RTX_PPL == 1, "tile classes: flat primary + shadow kernels");
+    const cptr<uint2> bclass = L.bin_class;
+#endif
+#else
+    const Launch& L = L0;
     KParams Q = *Pp;
 #if RTX_RAY_TABLE
     // The pixel's direction from the camera's table: its address needs the kernel arguments
@@ -870,8 +937,10 @@ __device__ __forceinline__ void render_body(const KParams* __restrict__ Pp, cons
     float* fbp = frame_fb(L);
     int64_t fbw = L.fstride;  // (pinned beside it only)
     if (!X) pin_uniform64(fbp, fbw);
+#endif
     const KParams& P = X ? *Pp : Q;  // (the hierarchy / texture kernels keep the pointer)
 #else
+    const Launch& L = L0;
     const KParams& P = *Pp;
     float* const fbp = frame_fb(L);
 #endif
